@@ -8,7 +8,14 @@ A "step" is one full energy+force forward exactly as the reference does it
 per MD step (implementations/matgl/pes.py:50-146): neighbor-list +
 partition build (native C++ builder, CPU) + the HIP-kernel model forward +
 the autograd force backward.  `value` = whole-job atom-steps/s over all
-ranks; config.breakdown reports graph-build vs model time separately.
+ranks; `ms_per_step` = wall milliseconds of one timed step.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` additionally times the judged scatter-add kernel inside the timed
+steps (the `roofline` field) and runs the CPU-oracle baseline leg (the
+`cpu_baseline` field); both are null in a plain run.  `--dump-outputs DIR`
+writes what the last timed step returned (energy, forces, ...) as
+DIR/<name>.npy so two builds can be compared output for output.
 
 Workloads (BASELINE.json configs; distmlip_amd/structures.py):
   si1m (default)  : diamond-Si 1,000,000 atoms fixed — THE config the
@@ -105,7 +112,15 @@ def parse_args():
                          "reuse the graph via Verlet-skin SKIN (A); the "
                          "headline line always uses per-step rebuilds")
     ap.add_argument("--no-bond-graph", action="store_true")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not "
+                         "need: the seg-sum roofline (HIP events inside the "
+                         "timed steps) and the CPU-oracle baseline leg")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline leg out")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (float32/float64)")
     ap.add_argument("--breakdown", action="store_true",
                     help="print per-stage timings (graph/H2D+fwd/bwd)")
     return ap.parse_args()
@@ -251,6 +266,38 @@ def cpu_baseline_leg(workload_name, threads):
     }
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # all files of one --dump-outputs run
+
+
+def dump_outputs(out, out_dir, rank, world):
+    """Write the arrays the last timed step returned as <name>.npy
+    (<name>_rank<r>.npy per rank for world > 1).  An array above its share
+    of the 64 MB budget is cut to a fixed, seeded sample of its rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, v in out.items():
+        if torch.is_tensor(v):
+            if v.dtype not in (torch.float32, torch.float64):
+                v = v.float()
+            a = v.detach().cpu().numpy()
+        elif isinstance(v, np.ndarray) and world > 1:
+            a = v                  # owned global ids: needed to align ranks
+        else:
+            continue
+        a = np.atleast_1d(a)
+        arrays[name] = a.astype(np.float64 if a.dtype.itemsize > 4
+                                else np.float32)
+    cap = DUMP_BUDGET_BYTES // (world * max(len(arrays), 1))
+    for name, a in arrays.items():
+        if a.nbytes > cap:
+            keep = max(1, cap // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(
+                a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        suffix = f"_rank{rank}" if world > 1 else ""
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", 0))
@@ -333,7 +380,9 @@ def main():
                       f"{len(v)} calls", file=sys.stderr)
         atexit.register(report)
 
-    timer = SegSumTimer(D=0 if (is_mace or is_uma) else 64).wrap()
+    timer = None
+    if args.full:
+        timer = SegSumTimer(D=0 if (is_mace or is_uma) else 64).wrap()
 
     graph_ms, model_ms = [], []
     for _ in range(args.warmup):
@@ -343,16 +392,19 @@ def main():
     if world > 1:
         torch.distributed.barrier()
 
-    timer.enabled = True
+    if timer is not None:
+        timer.enabled = True
+    out = None
     t0 = time.time()
     for _ in range(args.steps):
-        step()
+        out = step()
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     t1 = time.time()
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
 
     elapsed = t1 - t0
     if world > 1:
@@ -372,10 +424,13 @@ def main():
         except Exception as e:
             print(f"# tunableop write failed: {e}", file=sys.stderr)
 
+    if args.dump_outputs and out is not None:
+        dump_outputs(out, args.dump_outputs, rank, world)
+
     if rank == 0:
-        roofline = timer.summary()
+        roofline = timer.summary() if timer is not None else None
         cpu_b = None
-        if not args.skip_cpu_baseline and n_gpus == 1:
+        if args.full and not args.skip_cpu_baseline and n_gpus == 1:
             # cpu_baseline leg runs at N=1 only (tier contract)
             cpu_b = cpu_baseline_leg(args.workload, threads)
         line = {
