@@ -121,25 +121,23 @@ def _second_layer_packed(h, w2, b2, d: int):
     return torch.baddbmm(b2, hb, w2)
 
 
-_FUSED_BIG_ROWS = 40_000_000
-
-
 def _use_fused(rows: int) -> bool:
-    """Fused first-layer kernel policy.  Measured on li100k (same box,
-    run 25): in the GRAD-RECORDING path the fused kernel loses ~8%
-    step time to rocBLAS+gather-add (172 vs 187 ms), but in NO-GRAD
-    passes (checkpoint outer forward, inference) it skips the z save and
-    the [E,128] GEMM round-trip entirely (~4 GB vs ~9 GB of HBM per MLP),
-    so: fused iff grad is off — plus, for HUGE graphs (rows > 40M, where
-    a single [E,128] fp32 tensor is >20 GB), fused in the recording path
-    too: it materializes one fewer such transient per MLP, which is what
-    decides whether 2M atoms fit in 288 GB.  DM_FUSED_MLP=1 /
-    DM_NO_FUSED_MLP=1 force it on / off for A/B runs."""
-    if os.environ.get("DM_NO_FUSED_MLP", "0") == "1":
-        return False
-    if os.environ.get("DM_FUSED_MLP", "0") == "1":
-        return True
-    return not torch.is_grad_enabled() or rows > _FUSED_BIG_ROWS
+    """Fused first-layer kernel policy: on, in no-grad and in
+    grad-recording passes alike.  With the fp32-MFMA kernel the fused side
+    wins the recording-path A/B at li100k (same box, alternating runs,
+    op-by-op path, i.e. DM_WHOLE_GRAPH=0): 127.3 / 127.7 / 127.8 ms/step
+    fused against 137.0 / 137.1 / 137.1 unfused (rocBLAS + gather-add)
+    (profiles/r3_policy_li100k_opbyop_*.json).  The earlier VALU kernel
+    lost that A/B (187 vs 172 ms in run 25; 158 vs 137 re-measured next to
+    the numbers above), which is why recording passes used to stay unfused
+    below 40M rows.  In no-grad passes (checkpoint outer forward,
+    inference) the kernel also skips the z save and the [E,128] GEMM
+    round-trip (~4 GB vs ~9 GB of HBM per MLP), and in recording passes it
+    materializes one fewer [E,128] transient per MLP, which is what
+    decides whether 2M atoms fit in 288 GB.  `rows` is kept for callers
+    and for size-dependent policies.  DM_NO_FUSED_MLP=1 turns the kernel
+    off for A/B runs; DM_FUSED_MLP=1 is accepted and is the default."""
+    return os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
 
 
 def gated_mlp_split3(mlp: GatedMLP, v, e, pd, ops, d: int, w=None, base=None):

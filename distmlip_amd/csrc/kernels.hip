@@ -145,19 +145,139 @@ __global__ void k_gather_add4_v4(const float4* __restrict__ z1,
 // into the gather-add): for Din=64 -> Dout=128,
 //   z[e,:] = e_row[e,:] @ WT + bias + zs[src[e],:] + zd[dst[e],:]
 //   h      = silu(z)
-// Layout: one WAVE per edge, one LANE per pair of output columns
-// (l, l+64).  Each lane holds its two weight columns in 128 VGPRs (loaded
-// once per wave, L2-served); the edge index is wave-uniform
-// (readfirstlane) so the 64-float e-row comes through the SCALAR cache
-// and feeds v_fmac as the SGPR operand.  Every global access is
-// lane-contiguous: weight preload, zs/zd/zv row gathers (512 B/row), and
-// the z/h stores.  No LDS.  Saves materializing the [E,128] GEMM output
-// (~5.2 GB of HBM round-trip per MLP at li100k).
-// (Measured alternatives, run 21/22: LDS-broadcast weights were
-// issue-bound at 8.0 ms; two-edges-per-wave overflowed the SGPR file and
-// serialized at 4.1 ms; a one-column-per-lane split made the compiler
-// de-register the weight array.  This shape: 3.3 ms at li100k.)
+// Saves materializing the [E,128] GEMM output (~5.2 GB of HBM round-trip
+// per MLP at li100k).
+//
+// Layout: exact-fp32 MFMA tiles (v_mfma_f32_32x32x2_f32).  One WAVE owns a
+// tile of 32 edges x 128 output columns = 4 accumulators of 16 registers;
+// a block is 4 waves and the grid is capped (EDGE_MLP_MAX_BLOCKS) so each
+// wave walks many tiles and WT is staged once per block.
+//  * B operand: WT (32 KB) sits in LDS as float4 [k][c] = the four column
+//    blocks (c, 32+c, 64+c, 96+c) of row k, so ONE conflict-free
+//    ds_read_b128 per k-step feeds all four MFMAs of that step.
+//  * A operand without LDS: lane (r = lane&31, h = lane>>5) reads its own
+//    edge row as 8 float4s at floats [8i+4h, 8i+4h+4); MFMA step 4i+t
+//    then contracts k = 8i+4h+t on both operands.  The k order of the fma
+//    chain is permuted but fixed; every k is used exactly once.
+//  * Accumulators start at 0 and bias + gathered node rows are added in
+//    the epilogue, not folded into the accumulator init: a chain that
+//    starts at |bias+zs+zd| rounds every one of its 64 steps at that
+//    magnitude (about 2x the error of the unfused rocBLAS + gather-add
+//    path); starting at 0 keeps the error in the unfused path's class.
+//  * C layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5):
+//    each gather load / z / h store instruction covers two rows x 128 B;
+//    the four column blocks of a row are issued back to back.  Row
+//    indices are loaded once per tile (one per lane) and handed to the
+//    owning lanes by ds_bpermute.
+//  * Tails: loads of rows >= E are clamped to row E-1, stores predicated.
+// Resources (hipcc -O3, gfx950, kernel-resource-usage remarks):
+//   <2>: 157 VGPR, 0 AGPR, 74 SGPR, 32 KB LDS, 3 waves/SIMD, no scratch
+//   <3>: 143 VGPR, 0 AGPR, 78 SGPR, 32 KB LDS, 3 waves/SIMD, no scratch
+// Measured at si1m (rocprofv3 kernel trace): <2> at E = 46M rows, 48
+// launches, 14.1 ms average (13.6-16.3) against 42.83 ms (41.7-43.6) for
+// the VALU kernel; <3> at L = 12M rows, 30 launches, 4.42 ms (the VALU
+// kernel was not launched there: below 40M rows recording passes were
+// unfused).  The trace does not tell z-storing from no-z launches.  Stand-alone at E = 46M with synthetic indices: <2> 12.7 ms
+// no-z / 15.0 ms with z (VALU kernel 40.5 / 45.2), <3> 14.2 / 17.1 ms
+// (45.0 / 49.2).  Algorithmic bytes / 6.29 TB/s: 35.7 GB = 5.7 ms no-z,
+// 59.3 GB = 9.4 ms with z (+3.7 GB = 0.6 ms for <3>).
+// Where the rest goes (same stand-alone run, <2> no-z): without MFMA and
+// SiLU the load/gather/store skeleton alone takes 8.3 ms, the MFMAs add
+// ~4.4 ms (4.8 ms at the 157 TF peak) and the exact SiLU ~0.6-2 ms: the
+// matrix time does not hide behind the memory time.  None of these moved
+// it by more than 3 %: 4 waves/SIMD with gather batches of 2 or 4 rows,
+// prefetching the next tile's A rows across the epilogue, double-buffered
+// gather batches with the first one in flight during the MFMAs, 2
+// waves/SIMD with batches of 8 plus prefetch, a grid of 768 / 1024 / 1536
+// blocks, s_setprio(3) around the MFMA run (kept: 1-3 %).  A first
+// version with one row per gather batch and the compiler free to sink the
+// A loads into the MFMA loop ran 14.8 / 17.8 ms.  __expf/__frcp_rn SiLU
+// saved 0.8 ms and was rejected: results would no longer match.
+// History.  The first version was VALU: one wave per edge, one lane per
+// pair of output columns with its two weight columns in 128 VGPRs and the
+// e-row streamed through the scalar cache as the v_fmac SGPR operand, no
+// LDS: 3.3 ms at li100k (E = 5.03M), ~1530 cycles per edge, issue-bound.
+// (Measured alternatives to that shape, run 21/22: LDS-broadcast weights
+// were issue-bound at 8.0 ms; two-edges-per-wave overflowed the SGPR file
+// and serialized at 4.1 ms; a one-column-per-lane split made the compiler
+// de-register the weight array.)  The MFMA form needs 256 matrix-pipe
+// cycles per edge and leaves the VALU to the SiLU epilogue.
 // ---------------------------------------------------------------------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int EDGE_MLP_MAX_BLOCKS = 768;    // 256 CUs x 3 resident blocks
+
+inline int edge_mlp_blocks(int64_t rows) {
+    const int64_t tiles = (rows + 31) / 32;         // one 32-row tile per wave
+    const int64_t b = (tiles + BLOCK / 64 - 1) / (BLOCK / 64);
+    return (int)(b < 1 ? 1 : (b > EDGE_MLP_MAX_BLOCKS ? EDGE_MLP_MAX_BLOCKS : b));
+}
+
+// Epilogue of one tile: z = acc + bias + gathered rows, h = silu(z).
+// Rows are handled G at a time (8, or 4 in the 3-gather form: 64 / 48
+// registers of gathered values): all gather loads of a batch are issued
+// before any is consumed.  FULL tiles carry no per-row predicate.
+template <int NGATHER, bool FULL>
+__device__ __forceinline__ void edge_mlp_epilogue(
+        const f32x16 (&acc)[4], const float4 bcol,
+        const float* __restrict__ g0, const float* __restrict__ g1,
+        const float* __restrict__ g2, int32_t j0, int32_t j1, int32_t j2,
+        float* __restrict__ out, float* __restrict__ out_act,
+        int64_t base, int64_t E, int c, int h) {
+    constexpr int G = NGATHER == 3 ? 4 : 8;
+#pragma unroll
+    for (int rb = 0; rb < 16; rb += G) {
+        float gv[NGATHER][G][4];
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const float* p0 = g0 + (int64_t)__builtin_amdgcn_ds_bpermute(rl << 2, j0) * 128 + c;
+            const float* p1 = g1 + (int64_t)__builtin_amdgcn_ds_bpermute(rl << 2, j1) * 128 + c;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                gv[0][t][cb] = p0[32 * cb];
+                gv[1][t][cb] = p1[32 * cb];
+            }
+            if (NGATHER == 3) {
+                const float* p2 = g2 + (int64_t)__builtin_amdgcn_ds_bpermute(rl << 2, j2) * 128 + c;
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) gv[NGATHER - 1][t][cb] = p2[32 * cb];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t row = base + rl;
+            float z[4];
+            z[0] = acc[0][r] + bcol.x; z[1] = acc[1][r] + bcol.y;
+            z[2] = acc[2][r] + bcol.z; z[3] = acc[3][r] + bcol.w;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                z[cb] += gv[0][t][cb] + gv[1][t][cb];
+                if (NGATHER == 3) z[cb] += gv[NGATHER - 1][t][cb];
+            }
+            if (FULL || row < E) {
+                if (out) {                   // z saved for backward; skipped
+                    float* zp = out + row * 128 + c;   // in no-grad passes
+#pragma unroll
+                    for (int cb = 0; cb < 4; ++cb) zp[32 * cb] = z[cb];
+                }
+                // (a packed [2,E,64] h layout was tried to feed the
+                // second-layer bmm without a reshape, but the two distant
+                // 256 B plane stores cost more than the saved copies —
+                // profiles r21 vs r23)
+                float* hp = out_act + row * 128 + c;
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) hp[32 * cb] = siluf(z[cb]);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one row's SiLU at a time
+        }
+    }
+}
+
 template <int NGATHER>
 __global__ __launch_bounds__(256, 3)
 void k_edge_mlp_64x128(const float* __restrict__ erow,
@@ -172,46 +292,74 @@ void k_edge_mlp_64x128(const float* __restrict__ erow,
                        float* __restrict__ out,
                        float* __restrict__ out_act,
                        int64_t E) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int waves_per_block = blockDim.x >> 6;
-    float wlo[64], whi[64];
-#pragma unroll
-    for (int k = 0; k < 64; ++k) {
-        wlo[k] = WT[k * 128 + lane];
-        whi[k] = WT[k * 128 + 64 + lane];
+    // WT -> LDS, regrouped so one float4 holds the four column blocks
+    __shared__ float4 wlds[64 * 32];
+    for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
+        const float* w = WT + (i >> 5) * 128 + (i & 31);
+        wlds[i] = make_float4(w[0], w[32], w[64], w[96]);
     }
-    const float blo = bias[lane], bhi = bias[64 + lane];
-    for (int64_t edge = blockIdx.x * (int64_t)waves_per_block + wave;
-         edge < E; edge += (int64_t)gridDim.x * waves_per_block) {
-        const float* er = erow + edge * 64;    // wave-uniform -> scalar loads
-        float a0 = blo, a1 = bhi;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int c0 = lane & 31, h0 = lane >> 5;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+    const float4 bcol = make_float4(bias[c0], bias[32 + c0], bias[64 + c0],
+                                    bias[96 + c0]);
+    const float4* bl = wlds + (4 * h0) * 32 + c0;
+    const int64_t ntiles = (E + 31) >> 5;
+    const int64_t stride = (int64_t)gridDim.x * waves_per_block;
+    int64_t tile = blockIdx.x * (int64_t)waves_per_block + wave;
+
+    // lane (c, h): A fragment of row base+c, and that row's indices
+    float4 a[8];
+    int32_t n0 = 0, n1 = 0, n2 = 0;
+    auto load_tile = [&](int64_t t, int c, int h) {
+        const int64_t r = (t << 5) + c;
+        const int64_t lrow = r < E ? r : E - 1;   // clamp, never read past E
+        const float4* ap = (const float4*)(erow + lrow * 64) + h;
 #pragma unroll
-        for (int k = 0; k < 64; ++k) {
-            const float ek = er[k];
-            a0 = fmaf(ek, wlo[k], a0);
-            a1 = fmaf(ek, whi[k], a1);
+        for (int i = 0; i < 8; ++i) a[i] = ap[2 * i];
+        n0 = i0[lrow];
+        n1 = i1[lrow];
+        if (NGATHER == 3) n2 = i2[lrow];
+    };
+    for (; tile < ntiles; tile += stride) {
+        const int64_t base = tile << 5;
+        // re-derive (c, h) behind an opaque copy each tile: otherwise the
+        // per-register row offsets are hoisted out of the loop as ~30
+        // loop-invariant VGPRs and spilled
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int c = lane_t & 31, h = lane_t >> 5;
+        load_tile(tile, c, h);
+        __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
+        f32x16 acc[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[cb][r] = 0.0f;
+        // a wave inside its MFMA run outranks waves in their memory phases
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl[(8 * i + t) * 32];   // k = 8i + 4h + t
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.y, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.z, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.w, acc[3], 0, 0, 0);
+            }
         }
-        const float* r0 = g0 + (int64_t)i0[edge] * 128;
-        const float* r1 = g1 + (int64_t)i1[edge] * 128;
-        a0 += r0[lane] + r1[lane];
-        a1 += r0[64 + lane] + r1[64 + lane];
-        if (NGATHER == 3) {
-            const float* r2 = g2 + (int64_t)i2[edge] * 128;
-            a0 += r2[lane];
-            a1 += r2[64 + lane];
-        }
-        if (out) {                       // z saved for backward; skipped
-            float* zp = out + edge * 128;  // in no-grad passes
-            zp[lane] = a0;
-            zp[64 + lane] = a1;
-        }
-        // (a packed [2,E,64] h layout was tried to feed the second-layer
-        // bmm without a reshape, but the two distant 256 B plane stores
-        // cost more than the saved copies — profiles r21 vs r23)
-        float* hp = out_act + edge * 128;
-        hp[lane] = siluf(a0);
-        hp[64 + lane] = siluf(a1);
+        __builtin_amdgcn_s_setprio(0);
+        const int32_t j0 = n0, j1 = n1, j2 = n2;
+        if (base + 32 <= E)
+            edge_mlp_epilogue<NGATHER, true>(acc, bcol, g0, g1, g2, j0, j1, j2,
+                                             out, out_act, base, E, c, h);
+        else
+            edge_mlp_epilogue<NGATHER, false>(acc, bcol, g0, g1, g2, j0, j1,
+                                              j2, out, out_act, base, E, c, h);
     }
 }
 
@@ -1082,8 +1230,8 @@ int dm_edge_mlp3_f32(const float* erow, const float* WT, const float* bias,
         g_err = "edge_mlp fused kernel is compiled for Din=64, Dout=128";
         return -1;
     }
-    // one wave per edge: BLOCK threads cover BLOCK/64 edges per iter
-    k_edge_mlp_64x128<2><<<nblocks(E, BLOCK / 64), BLOCK, 0, s>>>(
+    // one wave per 32-edge tile, grid capped: waves loop over tiles
+    k_edge_mlp_64x128<2><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
         erow, WT, bias, zs, zd, nullptr, src, dst, nullptr, out, out_act, E);
     DM_CHECK_LAUNCH();
     return 0;
@@ -1099,7 +1247,7 @@ int dm_edge_mlp4_f32(const float* arow, const float* WT, const float* bias,
         g_err = "edge_mlp fused kernel is compiled for Din=64, Dout=128";
         return -1;
     }
-    k_edge_mlp_64x128<3><<<nblocks(L, BLOCK / 64), BLOCK, 0, s>>>(
+    k_edge_mlp_64x128<3><<<edge_mlp_blocks(L), BLOCK, 0, s>>>(
         arow, WT, bias, z1, z2, zv, lsrc, ldst, center, out, out_act, L);
     DM_CHECK_LAUNCH();
     return 0;

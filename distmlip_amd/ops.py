@@ -234,8 +234,9 @@ class _GatherAdd3(torch.autograd.Function):
 class _EdgeMlp3(torch.autograd.Function):
     """Fused first-layer edge MLP over the atom graph:
     (z, silu(z)) with z = erow @ WT + bias + zs[src] + zd[dst], the per-edge
-    GEMM computed INSIDE the gather kernel (LDS-resident WT) so the [E,2d]
-    GEMM output is never materialized.  WT/bias must be frozen (inference
+    GEMM computed INSIDE the gather kernel (exact-fp32 MFMA tiles of 32
+    edges per wave, WT staged in LDS) so the [E,2d] GEMM output is never
+    materialized.  WT/bias must be frozen (inference
     path) — their grads are not produced."""
 
     @staticmethod
