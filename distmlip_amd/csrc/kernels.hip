@@ -760,6 +760,95 @@ __global__ void k_nl(const double* __restrict__ pos,
     }
 }
 
+// ---------------------------------------------------------------------------
+// General-lattice variant: any non-singular cell, any pbc, any cell count.
+// The grid lives in FRACTIONAL space (nc cells per dim over the periodic
+// unit interval, or over the atoms' extent in an open dim); the stencil
+// walks UNWRAPPED cell indices a = c + d, d in [-R, R]: a periodic dim
+// folds a into image m = floor_div(a, nc) and cell a - m*nc, an open dim
+// skips a outside [0, nc).  Every (neighbor, image) pair is therefore
+// visited exactly once for any nc (nc = 1: same cell, images -R..R;
+// nc = 2: -1 and +1 are the same cell with different images).
+// Thread t handles center order[t] (cell-sorted walk: a wave shares its
+// candidate cells); rows are still addressed by atom id.  Lattice rows,
+// grid and flags are kernel arguments (scalar registers).
+// ---------------------------------------------------------------------------
+struct NlGrid {
+    double l[9];          // lattice rows, row-major
+    int32_t nc[3], R[3], per[3];
+};
+
+__device__ inline int32_t floor_div(int32_t a, int32_t n) {
+    return a >= 0 ? a / n : -((n - 1 - a) / n);
+}
+
+template <bool FILL>
+__global__ void k_nl_gen(const double* __restrict__ pos,
+                         const int32_t* __restrict__ cid,
+                         const int32_t* __restrict__ order,
+                         const int32_t* __restrict__ cell_start,
+                         NlGrid g, double r2tol, double tol, double br2tol,
+                         const int32_t* __restrict__ row_ptr,
+                         int32_t* __restrict__ cnt_or_src,
+                         int8_t* __restrict__ off_i8,
+                         uint8_t* __restrict__ bond_flag, int64_t N) {
+    const int32_t ncx = g.nc[0], ncy = g.nc[1], ncz = g.nc[2];
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < N; t += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t c = order[t];
+        const double xc = pos[3 * (int64_t)c], yc = pos[3 * (int64_t)c + 1],
+                     zc = pos[3 * (int64_t)c + 2];
+        const int32_t cc = cid[c];
+        const int32_t cx = cc / (ncy * ncz);
+        const int32_t cy = (cc / ncz) % ncy;
+        const int32_t cz = cc % ncz;
+        int32_t n_emit = 0;
+        int64_t w = FILL ? row_ptr[c] : 0;
+        for (int dx = -g.R[0]; dx <= g.R[0]; ++dx) {
+            int32_t ax = cx + dx, mx = 0;
+            if (g.per[0]) { mx = floor_div(ax, ncx); ax -= mx * ncx; }
+            else if (ax < 0 || ax >= ncx) continue;
+            for (int dy = -g.R[1]; dy <= g.R[1]; ++dy) {
+                int32_t ay = cy + dy, my = 0;
+                if (g.per[1]) { my = floor_div(ay, ncy); ay -= my * ncy; }
+                else if (ay < 0 || ay >= ncy) continue;
+                for (int dz = -g.R[2]; dz <= g.R[2]; ++dz) {
+                    int32_t az = cz + dz, mz = 0;
+                    if (g.per[2]) { mz = floor_div(az, ncz); az -= mz * ncz; }
+                    else if (az < 0 || az >= ncz) continue;
+                    // shift = m @ lattice (graph_build.cpp image shift)
+                    const double sx = mx * g.l[0] + my * g.l[3] + mz * g.l[6];
+                    const double sy = mx * g.l[1] + my * g.l[4] + mz * g.l[7];
+                    const double sz = mx * g.l[2] + my * g.l[5] + mz * g.l[8];
+                    const int32_t cell = (ax * ncy + ay) * ncz + az;
+                    const int32_t lo = cell_start[cell], hi = cell_start[cell + 1];
+                    for (int32_t q = lo; q < hi; ++q) {
+                        const int32_t j = order[q];
+                        if (j == c) continue;           // fpis.c:833
+                        const double ddx = pos[3 * (int64_t)j] + sx - xc;
+                        const double ddy = pos[3 * (int64_t)j + 1] + sy - yc;
+                        const double ddz = pos[3 * (int64_t)j + 2] + sz - zc;
+                        const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
+                        if (d2 < r2tol && d2 > tol) {
+                            if (FILL) {
+                                cnt_or_src[w] = j;
+                                off_i8[3 * w] = (int8_t)(-mx);      // off = -m
+                                off_i8[3 * w + 1] = (int8_t)(-my);
+                                off_i8[3 * w + 2] = (int8_t)(-mz);
+                                bond_flag[w] = (d2 < br2tol) ? 1 : 0;
+                                ++w;
+                            } else {
+                                ++n_emit;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (!FILL) cnt_or_src[c] = n_emit;
+    }
+}
+
 }  // namespace
 
 
@@ -1435,6 +1524,59 @@ int dm_nl_fill_f64(const double* pos, const int32_t* cid,
     k_nl<true><<<nblocks(N, BLOCK), BLOCK, 0, s>>>(
         pos, cid, order, cell_start, ncx, ncy, ncz, lx, ly, lz, r2tol, tol,
         br2tol, row_ptr, src, off_i8, bond_flag, N);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+// lattice9 / nc3 / R3 / pbc3 are HOST arrays; validated here so a bad plan
+// is an error, never an out-of-range cell index on the device
+static int nl_grid(const double* lattice9, const int32_t* nc3, const int32_t* R3,
+            const int32_t* pbc3, int64_t N, NlGrid* g) {
+    int64_t ncell = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (nc3[k] < 1 || R3[k] < 0) { g_err = "nl_gen: bad grid"; return -1; }
+        // image index |m| <= ceil(R/nc) must fit off_i8
+        if (pbc3[k] && (R3[k] + nc3[k] - 1) / nc3[k] > 127) {
+            g_err = "nl_gen: image index exceeds int8"; return -1;
+        }
+        g->nc[k] = nc3[k]; g->R[k] = R3[k]; g->per[k] = pbc3[k] ? 1 : 0;
+        ncell *= nc3[k];
+        if (ncell >= INT32_MAX) { g_err = "nl_gen: too many cells"; return -1; }
+    }
+    if (N >= INT32_MAX) { g_err = "nl_gen: N exceeds int32"; return -1; }
+    for (int k = 0; k < 9; ++k) g->l[k] = lattice9[k];
+    return 0;
+}
+
+int dm_nl_count_gen_f64(const double* pos, const int32_t* cid,
+                        const int32_t* order, const int32_t* cell_start,
+                        const double* lattice9, const int32_t* nc3,
+                        const int32_t* R3, const int32_t* pbc3,
+                        double r2tol, double tol, int32_t* cnt, int64_t N,
+                        uint64_t stream) {
+    NlGrid g;
+    if (int rc = nl_grid(lattice9, nc3, R3, pbc3, N, &g)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    k_nl_gen<false><<<nblocks(N, BLOCK), BLOCK, 0, s>>>(
+        pos, cid, order, cell_start, g, r2tol, tol, 0.0, nullptr, cnt,
+        nullptr, nullptr, N);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_nl_fill_gen_f64(const double* pos, const int32_t* cid,
+                       const int32_t* order, const int32_t* cell_start,
+                       const double* lattice9, const int32_t* nc3,
+                       const int32_t* R3, const int32_t* pbc3,
+                       double r2tol, double tol, double br2tol,
+                       const int32_t* row_ptr, int32_t* src, int8_t* off_i8,
+                       uint8_t* bond_flag, int64_t N, uint64_t stream) {
+    NlGrid g;
+    if (int rc = nl_grid(lattice9, nc3, R3, pbc3, N, &g)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    k_nl_gen<true><<<nblocks(N, BLOCK), BLOCK, 0, s>>>(
+        pos, cid, order, cell_start, g, r2tol, tol, br2tol, row_ptr, src,
+        off_i8, bond_flag, N);
     DM_CHECK_LAUNCH();
     return 0;
 }

@@ -1,12 +1,21 @@
-"""GPU-resident graph construction — the single-partition fast path
-(SURVEY §8(f).2): cell-list neighbor search on the GPU (fp64, exact
-replica of the CPU builder's edge condition) + bond/line graph assembly
-with torch GPU primitives.  Removes the per-step CPU rebuild + H2D of
-graph arrays for the 1-GPU path.
+"""GPU-resident graph construction: cell-list neighbor
+search on the GPU (fp64, exact replica of the CPU builder's edge
+condition) + bond/line graph assembly with torch GPU primitives.  Removes
+the per-step CPU rebuild + H2D of graph arrays.
 
-Scope guard: diagonal lattice, full PBC, >= 3 cells of >= cutoff per dim
-(every BASELINE workload qualifies); anything else falls back to the
-native CPU builder (also a product path — the general one).
+Two neighbor-list kernels share the pipeline (dispatch: `fast_scope`):
+
+  * fast path (`dm_nl_*_f64`): diagonal lattice, full PBC, >= 3 cells of
+    >= cutoff per dim — every BASELINE workload;
+  * general path (`dm_nl_*_gen_f64`): any non-singular lattice (triclinic,
+    sheared), any pbc combination, any box size, cells shorter than the
+    cutoff included.  The grid lives in fractional space (`cell_plan`).
+
+Scope guard (`supported`): False — the engines then fall back to the
+native CPU builder — only for a singular lattice, a cell so short that an
+image index would leave the int8 range of `off_i8`, a periodic fractional
+coordinate outside [0, 1) (wrapped coordinates are the builder contract),
+or an N / expected E beyond int32.
 """
 from __future__ import annotations
 
@@ -29,14 +38,146 @@ class GpuPD:
         return (None, self.line_row_ptr)
 
 
-def supported(structure, cutoff: float) -> bool:
-    lat = np.asarray(structure.lattice)
+INT32_MAX = 2 ** 31 - 1
+# cell_start stays O(N) for a sparse, huge box
+MAX_CELLS_PER_ATOM = 8
+MIN_CELL_CAP = 4096
+
+
+def fast_scope(lattice, pbc, cutoff: float) -> bool:
+    """Dispatch predicate: True routes to the diagonal `dm_nl_*_f64`
+    kernels (diagonal lattice, full PBC, >= 3 cells of >= cutoff per
+    dim), False to the general `dm_nl_*_gen_f64` pair."""
+    lat = np.asarray(lattice)
     if not np.allclose(lat, np.diag(np.diag(lat)), atol=1e-12):
         return False
-    if not all(int(x) for x in structure.pbc):
+    if not all(int(x) for x in pbc):
         return False
     d = np.diag(lat)
     return bool((d // cutoff >= 3).all())
+
+
+def cell_heights(lattice) -> np.ndarray:
+    """h_k = 1 / |column k of L^-1|: perpendicular height of the cell
+    along lattice vector k (|d frac_k| <= |d cart| / h_k)."""
+    inv = np.linalg.inv(np.asarray(lattice, dtype=np.float64))
+    return 1.0 / np.linalg.norm(inv, axis=0)
+
+
+def cell_plan(lattice, pbc, frac, cutoff: float, tol: float = 1e-8,
+              max_cells=None):
+    """Fractional-space cell grid of the general neighbor list (pure
+    numpy).  Returns (nc, R, origin, span), int64[3] / int64[3] /
+    float64[3] / float64[3].
+
+    Dim k spans [origin_k, origin_k + span_k] in fractional coordinates:
+    the unit interval if periodic, the atoms' extent if open.  With
+    rc = sqrt(cutoff^2 + tol) and h_k the perpendicular cell height,
+    nc_k = max(1, floor(span_k h_k / rc)) cells of perpendicular width
+    w_k = span_k h_k / nc_k, and the stencil reaches
+    R_k = ceil(rc / w_k) cells (1 whenever the dim holds a full cutoff).
+    An edge has |d frac_k| <= d / h_k < rc / h_k <= R_k cells, so the
+    unwrapped cells of its end points differ by at most R_k.  `max_cells`
+    caps prod(nc) by shrinking nc (bigger cells: R stays valid)."""
+    pbc = [bool(int(x)) for x in pbc]
+    frac = np.asarray(frac, dtype=np.float64).reshape(-1, 3)
+    h = cell_heights(lattice)
+    rc = float(np.sqrt(cutoff * cutoff + tol))
+    origin = np.zeros(3)
+    span = np.ones(3)
+    for k in range(3):
+        if not pbc[k] and len(frac):
+            lo, hi = float(frac[:, k].min()), float(frac[:, k].max())
+            origin[k], span[k] = lo, hi - lo
+    nc = np.ones(3, dtype=np.int64)
+    R = np.zeros(3, dtype=np.int64)
+    for k in range(3):
+        ext = span[k] * h[k]
+        nc[k] = max(1, int(np.floor(ext / rc)))
+        if ext > 0.0:
+            R[k] = int(np.ceil(rc / (ext / nc[k])))
+        if not pbc[k]:
+            R[k] = min(R[k], nc[k] - 1)     # cells outside [0, nc) are skipped
+    if max_cells is not None:
+        while int(nc.prod()) > max_cells:
+            f = (max_cells / float(nc.prod())) ** (1.0 / 3.0)
+            new = np.maximum(1, np.floor(nc * f).astype(np.int64))
+            if (new == nc).all():
+                new[int(np.argmax(nc))] -= 1
+            nc = new
+        for k in range(3):
+            if not pbc[k]:
+                R[k] = min(R[k], nc[k] - 1)
+    return nc, R, origin, span
+
+
+def cell_index(frac, nc, origin, span) -> np.ndarray:
+    """int64[N,3] cell of each atom under a `cell_plan` grid — the numpy
+    twin of the binning `build` does on the device."""
+    frac = np.asarray(frac, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(frac.shape, dtype=np.int64)
+    for k in range(3):
+        scale = nc[k] / span[k] if span[k] > 0.0 else 0.0
+        out[:, k] = np.clip(np.floor((frac[:, k] - origin[k]) * scale),
+                            0, nc[k] - 1).astype(np.int64)
+    return out
+
+
+def _cell_cap(n_atoms: int) -> int:
+    return max(MIN_CELL_CAP, MAX_CELLS_PER_ATOM * int(n_atoms))
+
+
+def supported(structure, cutoff: float, tol: float = 1e-8,
+              frac=None) -> bool:
+    """True when the GPU builder handles `structure`; see the module
+    docstring for the fallback conditions.  `frac` overrides
+    structure.frac_coords (the coordinates the build will bin)."""
+    lat = np.asarray(structure.lattice, dtype=np.float64)
+    pbc = [bool(int(x)) for x in structure.pbc]
+    if fast_scope(lat, pbc, cutoff):         # the fast path's own guard
+        return True
+    # singular lattice: the CPU builder's guard (graph_build.cpp)
+    if lat.shape != (3, 3) or not np.isfinite(lat).all() \
+            or abs(np.linalg.det(lat)) < 1e-12:
+        return False
+    frac = np.asarray(structure.frac_coords if frac is None else frac,
+                      dtype=np.float64)
+    N = len(frac)
+    if N == 0 or N >= INT32_MAX or not np.isfinite(frac).all():
+        return False
+    for k in range(3):
+        if pbc[k] and (frac[:, k].min() < 0.0 or frac[:, k].max() >= 1.0):
+            return False
+    nc, R, _, span = cell_plan(lat, pbc, frac, cutoff, tol)
+    # image index: |m_k| <= ceil(R_k / nc_k) must fit off_i8
+    for k in range(3):
+        if pbc[k] and -(-int(R[k]) // int(nc[k])) > 127:
+            return False
+    # expected E = N * density * cutoff sphere; an open dim thinner than
+    # the sphere counts as 2 rc thick (the sphere sticks out of the slab)
+    h = cell_heights(lat)
+    rc = float(np.sqrt(cutoff * cutoff + tol))
+    vol = abs(np.linalg.det(lat))
+    for k in range(3):
+        if not pbc[k]:
+            vol *= max(span[k], 2.0 * rc / h[k])
+    e_est = N * (N / vol) * (4.0 / 3.0) * np.pi * rc ** 3
+    return bool(2.0 * e_est < INT32_MAX)
+
+
+def engages(structure, cutoff: float, mode: str, tol: float = 1e-8,
+            frac=None) -> bool:
+    """The engines' `gpu_build` switch: "auto" — anything supported();
+    "fast" — only the diagonal fast-path scope (the pre-general-lattice
+    behaviour); "off" — never."""
+    if mode == "auto":
+        return supported(structure, cutoff, tol, frac=frac)
+    if mode == "fast":
+        return fast_scope(structure.lattice, structure.pbc, cutoff)
+    if mode == "off":
+        return False
+    raise ValueError(f"gpu_build must be 'auto', 'fast' or 'off', "
+                     f"got {mode!r}")
 
 
 def _csr_of(idx_sorted_key: torch.Tensor, n_rows: int, device):
@@ -292,18 +433,44 @@ def build(structure, cutoff, bond_cutoff, tol, use_bond_graph, device,
 
     lib = hip_lib()
     dev = torch.device(device)
-    lat = np.diag(np.asarray(structure.lattice)).astype(np.float64)
-    lx, ly, lz = (float(x) for x in lat)
+    lat33 = np.ascontiguousarray(structure.lattice, dtype=np.float64)
+    pbc = [int(bool(int(x))) for x in structure.pbc]
+    fast = fast_scope(lat33, pbc, cutoff)
     frac_np = frac_override if frac_override is not None \
         else structure.frac_coords
     frac = torch.tensor(np.asarray(frac_np), dtype=torch.float64, device=dev)
     N = frac.shape[0]
-    pos = frac * torch.tensor([lx, ly, lz], dtype=torch.float64, device=dev)
+    if fast:
+        lx, ly, lz = (float(x) for x in np.diag(lat33))
+        pos = frac * torch.tensor([lx, ly, lz], dtype=torch.float64,
+                                  device=dev)
+        nc = [max(3, int(d // cutoff)) for d in (lx, ly, lz)]
+        cxyz = [(frac[:, k] * nc[k]).long().clamp_(0, nc[k] - 1)
+                for k in range(3)]
+    else:
+        if abs(np.linalg.det(lat33)) < 1e-12:
+            raise RuntimeError("gpu_graph.build: singular lattice")
+        # cart = frac @ lattice in the CPU builder's term order
+        # (graph_build.cpp: u*row0 + v*row1 + w*row2)
+        lat_t = torch.tensor(lat33, dtype=torch.float64, device=dev)
+        pos = (frac[:, 0:1] * lat_t[0] + frac[:, 1:2] * lat_t[1]
+               + frac[:, 2:3] * lat_t[2])
+        nc_np, R_np, origin, span = cell_plan(
+            lat33, pbc, frac_np, cutoff, tol, max_cells=_cell_cap(N))
+        nc = [int(x) for x in nc_np]
+        # bin in fractional space; atoms outside the planned extent (only
+        # possible off-contract) are clamped into the edge cells
+        cxyz = []
+        for k in range(3):
+            scale = nc[k] / span[k] if span[k] > 0.0 else 0.0
+            cxyz.append(torch.floor((frac[:, k] - float(origin[k])) * scale)
+                        .long().clamp_(0, nc[k] - 1))
+        lat9 = (c_double * 9)(*lat33.reshape(-1).tolist())
+        nc3 = (c_int32 * 3)(*nc)
+        R3 = (c_int32 * 3)(*[int(x) for x in R_np])
+        pbc3 = (c_int32 * 3)(*pbc)
     pos = pos.contiguous()
-
-    nc = [max(3, int(d // cutoff)) for d in (lx, ly, lz)]
     ncx, ncy, ncz = nc
-    cxyz = [(frac[:, k] * nc[k]).long().clamp_(0, nc[k] - 1) for k in range(3)]
     cid = ((cxyz[0] * ncy + cxyz[1]) * ncz + cxyz[2]).to(torch.int32)
     order64 = torch.argsort(cid, stable=True)
     order = order64.to(torch.int32)
@@ -321,27 +488,42 @@ def build(structure, cutoff, bond_cutoff, tol, use_bond_graph, device,
     stream = c_uint64(torch.cuda.current_stream().cuda_stream)
     cnt = torch.empty(N, dtype=torch.int32, device=dev)
     r2tol = cutoff * cutoff + tol
-    _check(lib.dm_nl_count_f64(
-        fp(pos), ip(cid), ip(order), ip(cell_start), ncx, ncy, ncz,
-        c_double(lx), c_double(ly), c_double(lz), c_double(r2tol),
-        c_double(tol), ip(cnt), c_int64(N), stream), "dm_nl_count_f64")
+    if fast:
+        _check(lib.dm_nl_count_f64(
+            fp(pos), ip(cid), ip(order), ip(cell_start), ncx, ncy, ncz,
+            c_double(lx), c_double(ly), c_double(lz), c_double(r2tol),
+            c_double(tol), ip(cnt), c_int64(N), stream), "dm_nl_count_f64")
+    else:
+        _check(lib.dm_nl_count_gen_f64(
+            fp(pos), ip(cid), ip(order), ip(cell_start), lat9, nc3, R3,
+            pbc3, c_double(r2tol), c_double(tol), ip(cnt), c_int64(N),
+            stream), "dm_nl_count_gen_f64")
 
     row_ptr64 = torch.zeros(N + 1, dtype=torch.int64, device=dev)
     row_ptr64[1:] = torch.cumsum(cnt.long(), 0)
     E = int(row_ptr64[-1].item())
+    if E > INT32_MAX:
+        raise RuntimeError(f"gpu_graph.build: {E} edges exceed int32")
     row_ptr = row_ptr64.to(torch.int32)
 
     src = torch.empty(E, dtype=torch.int32, device=dev)
     off_i8 = torch.empty(E, 3, dtype=torch.int8, device=dev)
     bond_flag = torch.empty(E, dtype=torch.uint8, device=dev)
     br2tol = bond_cutoff * bond_cutoff + tol
-    _check(lib.dm_nl_fill_f64(
-        fp(pos), ip(cid), ip(order), ip(cell_start), ncx, ncy, ncz,
-        c_double(lx), c_double(ly), c_double(lz), c_double(r2tol),
-        c_double(tol), c_double(br2tol), ip(row_ptr), ip(src),
-        ctypes.cast(off_i8.data_ptr(), POINTER(ctypes.c_int8)),
-        ctypes.cast(bond_flag.data_ptr(), POINTER(ctypes.c_uint8)),
-        c_int64(N), stream), "dm_nl_fill_f64")
+    off_p = ctypes.cast(off_i8.data_ptr(), POINTER(ctypes.c_int8))
+    flag_p = ctypes.cast(bond_flag.data_ptr(), POINTER(ctypes.c_uint8))
+    if fast:
+        _check(lib.dm_nl_fill_f64(
+            fp(pos), ip(cid), ip(order), ip(cell_start), ncx, ncy, ncz,
+            c_double(lx), c_double(ly), c_double(lz), c_double(r2tol),
+            c_double(tol), c_double(br2tol), ip(row_ptr), ip(src),
+            off_p, flag_p, c_int64(N), stream), "dm_nl_fill_f64")
+    else:
+        _check(lib.dm_nl_fill_gen_f64(
+            fp(pos), ip(cid), ip(order), ip(cell_start), lat9, nc3, R3,
+            pbc3, c_double(r2tol), c_double(tol), c_double(br2tol),
+            ip(row_ptr), ip(src), off_p, flag_p, c_int64(N), stream),
+            "dm_nl_fill_gen_f64")
 
     dst = torch.repeat_interleave(
         torch.arange(N, device=dev, dtype=torch.int32), cnt.long())

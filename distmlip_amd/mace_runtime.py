@@ -43,7 +43,7 @@ class MaceSpmdEngine:
 
     def __init__(self, core: MACECore, world: int, threads: int = 8,
                  device: Optional[str] = None, ops=None,
-                 checkpoint: str = "auto"):
+                 checkpoint: str = "auto", gpu_build: str = "auto"):
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         assert world == 1 or dist.is_initialized()
         self.world = world
@@ -56,6 +56,12 @@ class MaceSpmdEngine:
         self.ops = ops if ops is not None else default_ops_factory(self.device)
         self.threads = threads
         self.checkpoint = checkpoint
+        # GPU graph build: "auto" (anything gpu_graph.supported()),
+        # "fast" (diagonal full-PBC >= 3-cell scope only) or "off"
+        if gpu_build not in ("auto", "fast", "off"):
+            raise ValueError(f"gpu_build must be 'auto', 'fast' or 'off', "
+                             f"got {gpu_build!r}")
+        self.gpu_build = gpu_build
         self.float_th = self.core.node_embedding.dtype
 
     def build_graph(self, structure) -> Distributed:
@@ -84,7 +90,8 @@ class MaceSpmdEngine:
             if (dev.type == "cuda"
                     and not getattr(self.ops, "is_reference", False)
                     and _os.environ.get("DM_NO_GPU_BUILD") != "1"
-                    and gpu_graph.supported(structure, cfg.r_max)):
+                    and gpu_graph.engages(structure, cfg.r_max,
+                                          self.gpu_build)):
                 if P == 1:
                     gpu_pd = gpu_graph.build(structure, cfg.r_max, 0.0,
                                              1e-8, False, dev)

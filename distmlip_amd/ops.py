@@ -98,6 +98,17 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_rbf_env_bwd_f32.restype = c_int32
         lib.dm_rbf_env_bwd_f32.argtypes = [fp, fp, fp, cf, c_int32, c_int32,
                                            fp, c_int64, c_uint64]
+        dp = POINTER(ctypes.c_double)
+        cd = ctypes.c_double
+        # pos, cid, order, cell_start | host: lattice9, nc3, R3, pbc3
+        nl_gen = [dp, ip, ip, ip, dp, ip, ip, ip]
+        lib.dm_nl_count_gen_f64.restype = c_int32
+        lib.dm_nl_count_gen_f64.argtypes = nl_gen + [cd, cd, ip, c_int64,
+                                                     c_uint64]
+        lib.dm_nl_fill_gen_f64.restype = c_int32
+        lib.dm_nl_fill_gen_f64.argtypes = nl_gen + [
+            cd, cd, cd, ip, ip, POINTER(ctypes.c_int8),
+            POINTER(ctypes.c_uint8), c_int64, c_uint64]
         lib.dm_hip_last_error.restype = c_char_p
         _hip_lib = lib
     return _hip_lib

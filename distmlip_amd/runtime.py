@@ -226,9 +226,14 @@ class SpmdEngine:
         # Halo exchanges stay OUTSIDE checkpointed segments (a re-run of a
         # comm op during backward would desynchronize the ranks).
         self.checkpoint = checkpoint
-        # GPU-resident graph build for the single-partition path
-        # (distmlip_amd/gpu_graph.py); "auto" engages on diagonal-lattice
-        # full-PBC structures when world == 1 and no custom backend is set
+        # GPU-resident graph build (distmlip_amd/gpu_graph.py) when no
+        # custom backend is set: "auto" engages on everything
+        # gpu_graph.supported() accepts (any non-singular lattice, any
+        # pbc), "fast" only on the diagonal full-PBC >= 3-cell scope,
+        # "off" never
+        if gpu_build not in ("auto", "fast", "off"):
+            raise ValueError(f"gpu_build must be 'auto', 'fast' or 'off', "
+                             f"got {gpu_build!r}")
         self.gpu_build = gpu_build
 
     # -- graph ------------------------------------------------------------
@@ -310,11 +315,12 @@ class SpmdEngine:
         gpu_pd = None
         if dist_info is None:
             from distmlip_amd import gpu_graph
-            if (self.gpu_build == "auto"
-                    and self.graph_backend is None
+            if (self.graph_backend is None
                     and dev.type == "cuda"
                     and _os.environ.get("DM_NO_GPU_BUILD") != "1"
-                    and gpu_graph.supported(structure, cfg.cutoff)):
+                    and gpu_graph.engages(structure, cfg.cutoff,
+                                          self.gpu_build,
+                                          frac=frac_override)):
                 if P == 1:
                     gpu_pd = gpu_graph.build(
                         structure, cfg.cutoff, cfg.three_body_cutoff, 1e-8,

@@ -36,7 +36,8 @@ class UmaSpmdEngine:
 
     def __init__(self, core: UMACore, world: int, threads: int = 8,
                  device: Optional[str] = None, ops=None,
-                 checkpoint: str = "auto", autocast_bf16: bool = False):
+                 checkpoint: str = "auto", autocast_bf16: bool = False,
+                 gpu_build: str = "auto"):
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         assert world == 1 or dist.is_initialized()
         self.world = world
@@ -49,6 +50,12 @@ class UmaSpmdEngine:
         self.ops = ops if ops is not None else default_ops_factory(self.device)
         self.threads = threads
         self.checkpoint = checkpoint
+        # GPU graph build: "auto" (anything gpu_graph.supported()),
+        # "fast" (diagonal full-PBC >= 3-cell scope only) or "off"
+        if gpu_build not in ("auto", "fast", "off"):
+            raise ValueError(f"gpu_build must be 'auto', 'fast' or 'off', "
+                             f"got {gpu_build!r}")
+        self.gpu_build = gpu_build
         self.autocast_bf16 = autocast_bf16
         self.float_th = self.core.sphere_embedding.dtype
 
@@ -76,7 +83,8 @@ class UmaSpmdEngine:
             if (dev.type == "cuda"
                     and not getattr(self.ops, "is_reference", False)
                     and _os.environ.get("DM_NO_GPU_BUILD") != "1"
-                    and gpu_graph.supported(structure, cfg.cutoff)):
+                    and gpu_graph.engages(structure, cfg.cutoff,
+                                          self.gpu_build)):
                 if P == 1:
                     gpu_pd = gpu_graph.build(structure, cfg.cutoff, 0.0,
                                              1e-8, False, dev)

@@ -152,6 +152,33 @@ int dm_nl_fill_f64(const double* pos, const int32_t* cid,
                    const int32_t* row_ptr, int32_t* src, int8_t* off_i8,
                    uint8_t* bond_flag, int64_t N, uint64_t stream);
 
+/* General-lattice GPU neighbor list: any non-singular cell (triclinic /
+ * sheared), any pbc combination, any cell count per dim (cells shorter
+ * than the cutoff included).  Same emitted-edge contract as above
+ * (fpis.c:418-901; edge condition fpis.c:833) and the same pre-binned
+ * inputs, but the grid lives in FRACTIONAL space: dim k has `nc3[k]`
+ * cells and a stencil radius `R3[k]`; a periodic dim (pbc3[k] != 0) folds
+ * the unwrapped cell index c+d into (image, cell) by floor division, an
+ * open dim skips indices outside [0, nc).  The image shift is
+ * m @ lattice with `lattice9` the row-major lattice ROWS.  Threads walk
+ * centers in `order` (cell-sorted); rows are addressed by atom id.
+ * pos/cid/order/cell_start/row_ptr and the outputs are DEVICE arrays;
+ * lattice9/nc3/R3/pbc3 are small HOST arrays passed on to the kernel by
+ * value.  Fails (nonzero) if an image index could exceed int8. */
+int dm_nl_count_gen_f64(const double* pos, const int32_t* cid,
+                        const int32_t* order, const int32_t* cell_start,
+                        const double* lattice9, const int32_t* nc3,
+                        const int32_t* R3, const int32_t* pbc3,
+                        double r2tol, double tol, int32_t* cnt, int64_t N,
+                        uint64_t stream);
+int dm_nl_fill_gen_f64(const double* pos, const int32_t* cid,
+                       const int32_t* order, const int32_t* cell_start,
+                       const double* lattice9, const int32_t* nc3,
+                       const int32_t* R3, const int32_t* pbc3,
+                       double r2tol, double tol, double br2tol,
+                       const int32_t* row_ptr, int32_t* src, int8_t* off_i8,
+                       uint8_t* bond_flag, int64_t N, uint64_t stream);
+
 /* MACE uvu tensor product, fused per edge (round 2).  Replaces the
  * e3nn TensorProduct the reference's MACE interactions delegate to
  * (implementations/mace/models.py:144-152, conv_tp of
