@@ -140,20 +140,36 @@ def _use_fused(rows: int) -> bool:
     return os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
 
 
+def _use_fused_tail(ops, d: int, wcg) -> bool:
+    """Fused reverse tail policy (ops.mlp_tail: second layer + combine as
+    one autograd node whose backward is one kernel from go to dz): on for
+    d = 64 with frozen weights on a backend that has it.  The caller adds
+    the per-call condition that h requires grad, so no-grad passes keep the
+    plain path.  DM_NO_FUSED_MLP_BWD=1 restores the three-kernel chain
+    (gated_combine_bwd, two GEMMs, silu_bwd) for A/B runs in one build."""
+    return (d == 64 and not wcg.requires_grad and hasattr(ops, "mlp_tail")
+            and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1")
+
+
 def gated_mlp_split3(mlp: GatedMLP, v, e, pd, ops, d: int, w=None, base=None):
     """GatedMLP over cat(v[src], v[dst], e) via split-linear + one 2h-wide
     gather_add3, finished by the fused gated-combine epilogue:
     returns base + silu(core2(silu(z_c))) * sigmoid(gate2(silu(z_g))) * w."""
     wcg, bcg, w2, b2, fusedT = _packed_weights(mlp)
     ws, wd = wcg[:, :d], wcg[:, d:2 * d]
+    tail = _use_fused_tail(ops, d, wcg)
     if (d == 64 and not wcg.requires_grad and _use_fused(e.shape[0])
             and hasattr(ops, "edge_mlp3_act")):
         # per-edge GEMM fused into the gather kernel (no [E,2d] transient)
-        h = ops.edge_mlp3_act(e, fusedT, bcg, v @ ws.t(), v @ wd.t(), pd)
+        first = ops.edge_mlp3_zh if tail else ops.edge_mlp3_act
+        zh = first(e, fusedT, bcg, v @ ws.t(), v @ wd.t(), pd)
     else:
         we = wcg[:, 2 * d:]
-        h = ops.gather_add3_act(v @ ws.t(), v @ wd.t(),
-                                torch.addmm(bcg, e, we.t()), pd)
+        first = ops.gather_add3_zh if tail else ops.gather_add3_act
+        zh = first(v @ ws.t(), v @ wd.t(), torch.addmm(bcg, e, we.t()), pd)
+    z, h = zh if tail else (None, zh)
+    if tail and h.requires_grad:
+        return ops.mlp_tail(z, h, w2, b2, w, base)
     cg = _second_layer_packed(h, w2, b2, d)
     return ops.gated_combine_packed(cg, w, base)
 
@@ -163,14 +179,19 @@ def gated_mlp_split4(mlp: GatedMLP, n, a, v, pd, ops, d: int, w=None,
     """GatedMLP over cat(n[l_src], n[l_dst], a, v[center]), same structure."""
     wcg, bcg, w2p, b2p, fusedT = _packed_weights(mlp)
     w1, w2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
+    tail = _use_fused_tail(ops, d, wcg)
     if (d == 64 and not wcg.requires_grad and _use_fused(a.shape[0])
             and hasattr(ops, "edge_mlp4_act")):
-        h = ops.edge_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ w2.t(),
-                              v @ wv.t(), pd)
+        first = ops.edge_mlp4_zh if tail else ops.edge_mlp4_act
+        zh = first(a, fusedT, bcg, n @ w1.t(), n @ w2.t(), v @ wv.t(), pd)
     else:
         wa = wcg[:, 2 * d:3 * d]
-        h = ops.gather_add4_act(n @ w1.t(), n @ w2.t(),
-                                torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
+        first = ops.gather_add4_zh if tail else ops.gather_add4_act
+        zh = first(n @ w1.t(), n @ w2.t(), torch.addmm(bcg, a, wa.t()),
+                   v @ wv.t(), pd)
+    z, h = zh if tail else (None, zh)
+    if tail and h.requires_grad:
+        return ops.mlp_tail(z, h, w2p, b2p, w, base)
     cg = _second_layer_packed(h, w2p, b2p, d)
     return ops.gated_combine_packed(cg, w, base)
 

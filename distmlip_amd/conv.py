@@ -40,6 +40,18 @@ def _second_bwd(dcg, w2, d):
     return dh
 
 
+def _mlp_tail_bwd(ops, go, cg, w, z, w2, d):
+    """(dz, dw) from the gradient go of r_combine_fwd(cg, w, base): one
+    kernel where the backend has r_mlp_tail_bwd (d = 64), else combine
+    reverse + second-layer GEMMs + silu reverse.  DM_NO_FUSED_MLP_BWD=1
+    forces the latter for A/B runs."""
+    if (d == 64 and hasattr(ops, "r_mlp_tail_bwd")
+            and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1"):
+        return ops.r_mlp_tail_bwd(go, cg, w, z, w2)
+    dcg, dw = ops.r_combine_bwd(go, cg, w)
+    return ops.r_silu_bwd(_second_bwd(dcg, w2, d), z), dw
+
+
 def _unpack_edge(packs, d):
     wcg, bcg, w2, b2 = packs
     return wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:], bcg, w2, b2
@@ -78,8 +90,7 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     # node MLP reverse (v2 = v + seg_dst(msg))
     if go_v2 is not None:
         dmsg = ops.r_gather_dst(go_v2, pd)
-        dcg2, dwab = ops.r_combine_bwd(dmsg, cg2, wab)
-        dz2 = ops.r_silu_bwd(_second_bwd(dcg2, w22, d), z2)
+        dz2, dwab = _mlp_tail_bwd(ops, dmsg, cg2, wab, z2, w22, d)
         # e2 grad: external + the node MLP's per-edge GEMM, fused
         ge2 = (torch.addmm(go_e2, dz2, we2) if go_e2 is not None
                else dz2 @ we2)
@@ -88,8 +99,7 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
         ge2 = go_e2
 
     # edge MLP reverse (e2 = e + combine(cg1, wbb))
-    dcg1, dwbb = ops.r_combine_bwd(ge2, cg1, wbb)
-    dz1 = ops.r_silu_bwd(_second_bwd(dcg1, w21, d), z1)
+    dz1, dwbb = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
     ge = torch.addmm(ge2, dz1, we1)      # base passthrough + GEMM
     # v grad: passthrough + all four per-node GEMM backs, fused
     gv = torch.addmm(go_v2, ops.r_seg_src(dz1, pd), ws1) \
@@ -176,8 +186,7 @@ def bond_bwd(ops, pd, saved, packs, d, go_n2, mask_l=None,
                        wcg[:, 3 * d:])
     go_n2 = go_n2.contiguous()
     dmsg = ops.r_gather_ldst(go_n2, pd)
-    dcg, dwl = ops.r_combine_bwd(dmsg, cg, wl)
-    dz = ops.r_silu_bwd(_second_bwd(dcg, w2, d), z)
+    dz, dwl = _mlp_tail_bwd(ops, dmsg, cg, wl, z, w2, d)
     if acc_a is not None:
         acc_a.addmm_(dz, wa)
         da = None
@@ -221,8 +230,7 @@ def angle_bwd(ops, pd, saved, packs, d, go_a2, acc_n=None, acc_v=None):
     w1, wn2, wa, wv = (wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:3 * d],
                        wcg[:, 3 * d:])
     go_a2 = go_a2.contiguous()
-    dcg, _ = ops.r_combine_bwd(go_a2, cg, None)
-    dz = ops.r_silu_bwd(_second_bwd(dcg, w2, d), z)
+    dz, _ = _mlp_tail_bwd(ops, go_a2, cg, None, z, w2, d)
     da = torch.addmm(go_a2, dz, wa)
     if acc_n is not None:
         gn = None
@@ -558,10 +566,8 @@ def atom_bwd_recompute(ops, pd, v_in, e_in, wbb, wab, pe, pn, d,
         cg2 = _second_fwd(h2, w22, pn[3], d)
         del h2
         dmsg = ops.r_gather_dst(go_v2, pd)
-        dcg2, dwab = ops.r_combine_bwd(dmsg, cg2, wab)
-        del dmsg, cg2
-        dz2 = ops.r_silu_bwd(_second_bwd(dcg2, w22, d), z2)
-        del dcg2, z2
+        dz2, dwab = _mlp_tail_bwd(ops, dmsg, cg2, wab, z2, w22, d)
+        del dmsg, cg2, z2
         ge2 = (torch.addmm(go_e2, dz2, we2) if go_e2 is not None
                else dz2 @ we2)
         acc_wab.add_(dwab)
@@ -574,10 +580,8 @@ def atom_bwd_recompute(ops, pd, v_in, e_in, wbb, wab, pe, pn, d,
                                torch.addmm(bcg1, e_in, we1.t()), pd)
     cg1 = _second_fwd(h1, w21, pe[3], d)
     del h1
-    dcg1, dwbb = ops.r_combine_bwd(ge2, cg1, wbb)
-    del cg1
-    dz1 = ops.r_silu_bwd(_second_bwd(dcg1, w21, d), z1)
-    del dcg1, z1
+    dz1, dwbb = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
+    del cg1, z1
     ge = torch.addmm(ge2, dz1, we1)
     del ge2
     gv = torch.addmm(go_v2, ops.r_seg_src(dz1, pd), ws1) \

@@ -688,6 +688,231 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 }
 
 // ---------------------------------------------------------------------------
+// Fused reverse tail of one gated MLP (d = 64): from the gradient go of
+//   out = base + silu(c) * sigmoid(g) * w,  c|g = h[:, :64]|h[:, 64:] @ w2c|w2g
+//   h = silu(z)
+// straight to dz, in one pass:
+//   dc = go*w*sig(g)*silu'(c)   dg = go*w*silu(c)*sig(g)*(1-sig(g))
+//   dw = go*silu(c)*sig(g)
+//   dh[:, :64] = dc @ w2c^T     dh[:, 64:] = dg @ w2g^T     dz = dh*silu'(z)
+// It replaces k_gated_combine_bwd + two rocBLAS GEMMs + k_silu_bwd; dc|dg
+// ([2,E,64]) and dh ([E,128]) are never written to memory.  The scalar
+// expressions are those of k_gated_combine_bwd and k_silu_bwd (exact expf
+// and division).
+//
+// Skeleton of k_edge_mlp_64x128: one wave owns 32 rows x 128 dh columns =
+// 4 accumulators (v_mfma_f32_32x32x2_f32, starting at 0), 4 waves per
+// block, grid capped by edge_mlp_blocks so both weight blocks are staged
+// once per block.
+//  * B operand: LDS float4 [k][col] = (w2c[col][k], w2c[32+col][k],
+//    w2g[col][k], w2g[32+col][k]) — the transposes of the two 64x64 blocks,
+//    32 KB; one ds_read_b128 per k-step feeds the four MFMAs of that step.
+//  * A operand: lane (r = lane&31, h = lane>>5) loads go/c/g/w of its own
+//    row at floats [8i+4h, 8i+4h+4), computes dc and dg there (64 registers
+//    once all 8 slices are done), and stores its dw slice from there.  MFMA
+//    step 4i+t contracts k = 8i+4h+t; accumulators 0,1 take dc as A and
+//    2,3 take dg.  The slices are loaded and consumed TAIL_CHUNK at a time
+//    so that at most 4*4*TAIL_CHUNK registers of inputs are live.
+//  * Epilogue in the accumulator layout (col = lane&31, row = (reg&3) +
+//    8*(reg>>2) + 4*(lane>>5)): z is loaded 8 rows at a time (all loads of
+//    a batch in flight before any is used), dz = acc * silu'(z) stored.
+//  * Tails: a lane whose row is >= E skips the A phase altogether (no
+//    loads, no dw store, zeros as A operand); z loads of such rows are
+//    clamped to row E-1 and the dz stores predicated.  All row offsets are
+//    64-bit (E x 128 floats passes 2^31 at si1m).
+// Resources (hipcc -O3, gfx950, kernel-resource-usage remarks):
+//   <true>  (w, dw): 146 VGPR, 0 AGPR, 72 SGPR, 32 KB LDS, 3 waves/SIMD,
+//                    no scratch
+//   <false> (no w):  146 VGPR, 0 AGPR, 68 SGPR, 32 KB LDS, 3 waves/SIMD,
+//                    no scratch
+// Measured at si1m (rocprofv3 kernel trace, 3 steps): at E = 46M rows with
+// w, 24 launches, 22.5 ms average (21.9-23.6); at L = 12M rows 6.5 ms with
+// w (9 launches) and 5.0 ms without (6).  The chain it replaces took, in
+// the parent's trace of the same run, 13.5 + 2 x 5.6 + 11.8 = 36.5 ms at
+// 46M rows.  Algorithmic bytes at 46M rows: 106 GB = 16.8 ms at 6.29 TB/s
+// (82.4 GB = 13.1 ms without w and dw).  Stand-alone on random inputs:
+// 24.9 ms with w, 19.1 ms without (chain: 39.1 / 35.5); both forms move
+// their bytes at the same 4.3 TB/s, i.e. the dw stores in the A layout
+// (lanes 256 B apart, 32 B per pair of lanes) cost what their bytes cost
+// and no more, which is why they were not staged through LDS (8 KB more
+// per wave would also take the kernel from 3 blocks per CU to 2).
+// Tried (stand-alone, 46M rows, with w / without):
+//  * TAIL_CHUNK 2 / 4 / 8: 26.3 / 25.2 / 25.2 ms with w, 19.4 / 19.3 /
+//    19.0 without; 146-148 VGPR in all three.  4 kept.
+//  * nontemporal dz and dw stores (with or without nontemporal z loads):
+//    29.7 ms with w, 19.0 without.  Rejected.
+//  * a predicate on each dw store instead of one around the A phase: 16
+//    basic blocks, 168 VGPR and 47 spilled (176-184 B scratch per lane).
+//    Never run.
+// ---------------------------------------------------------------------------
+constexpr int TAIL_CHUNK = 4;    // row slices (of 8) per load batch
+
+template <bool FULL>
+__device__ __forceinline__ void mlp_tail_epilogue(
+        const f32x16 (&acc)[4], const float* __restrict__ z,
+        float* __restrict__ dz, int64_t base, int64_t E, int c, int h) {
+    constexpr int G = 8;
+#pragma unroll
+    for (int rb = 0; rb < 16; rb += G) {
+        float zv[G][4];
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t row = base + rl;
+            const int64_t lrow = (FULL || row < E) ? row : E - 1;
+            const float* zp = z + lrow * 128 + c;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) zv[t][cb] = zp[32 * cb];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t row = base + rl;
+            if (FULL || row < E) {
+                float* dp = dz + row * 128 + c;
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) {
+                    const float x = zv[t][cb];
+                    const float s = 1.0f / (1.0f + expf(-x));
+                    dp[32 * cb] = acc[cb][r] * (s * (1.0f + x * (1.0f - s)));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one row at a time
+        }
+    }
+}
+
+// A phase of one tile for one lane: dc|dg of the 32 floats it owns of its
+// row (offset off = row * 64 + 4h), dw stored from there.
+template <bool HAS_W>
+__device__ __forceinline__ void mlp_tail_a_phase(
+        const float* __restrict__ go, const float* __restrict__ cp,
+        const float* __restrict__ gp, const float* __restrict__ wp,
+        float* __restrict__ dw, int64_t off, float (&dcv)[32],
+        float (&dgv)[32]) {
+#pragma unroll
+    for (int i0 = 0; i0 < 8; i0 += TAIL_CHUNK) {
+        float4 vgo[TAIL_CHUNK], vc[TAIL_CHUNK], vg[TAIL_CHUNK],
+            vw[TAIL_CHUNK];
+#pragma unroll
+        for (int j = 0; j < TAIL_CHUNK; ++j) {
+            const int64_t o = off + 8 * (i0 + j);
+            vgo[j] = *(const float4*)(go + o);
+            vc[j] = *(const float4*)(cp + o);
+            vg[j] = *(const float4*)(gp + o);
+            if (HAS_W) vw[j] = *(const float4*)(wp + o);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // the batch in flight first
+#pragma unroll
+        for (int j = 0; j < TAIL_CHUNK; ++j) {
+            const float gov4[4] = {vgo[j].x, vgo[j].y, vgo[j].z, vgo[j].w};
+            const float cv4[4] = {vc[j].x, vc[j].y, vc[j].z, vc[j].w};
+            const float gv4[4] = {vg[j].x, vg[j].y, vg[j].z, vg[j].w};
+            float wv4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+            if (HAS_W) {
+                wv4[0] = vw[j].x; wv4[1] = vw[j].y;
+                wv4[2] = vw[j].z; wv4[3] = vw[j].w;
+            }
+            float dwv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float gov = gov4[t], cv = cv4[t], gv = gv4[t];
+                const float sc = sigf(cv), sg = sigf(gv);
+                const float silu_c = cv * sc;
+                const float wv = wv4[t];
+                dcv[4 * (i0 + j) + t] =
+                    gov * wv * sg * (sc * (1.0f + cv * (1.0f - sc)));
+                dgv[4 * (i0 + j) + t] =
+                    gov * wv * silu_c * (sg * (1.0f - sg));
+                dwv[t] = gov * silu_c * sg;
+            }
+            if (HAS_W)
+                *(float4*)(dw + off + 8 * (i0 + j)) =
+                    make_float4(dwv[0], dwv[1], dwv[2], dwv[3]);
+            __builtin_amdgcn_sched_barrier(0);   // one slice at a time
+        }
+    }
+}
+
+template <bool HAS_W>
+__global__ __launch_bounds__(256, 3)
+void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]
+                          const float* __restrict__ cp,   // [E,64]
+                          const float* __restrict__ gp,   // [E,64]
+                          const float* __restrict__ wp,   // [E,64], HAS_W
+                          const float* __restrict__ z,    // [E,128]
+                          const float* __restrict__ w2c,  // [64,64] in x out
+                          const float* __restrict__ w2g,
+                          float* __restrict__ dz,         // [E,128]
+                          float* __restrict__ dw,         // [E,64], HAS_W
+                          int64_t E) {
+    __shared__ float4 wlds[64 * 32];
+    // i = (col, k) with k fastest: coalesced reads of the row-major blocks
+    for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
+        const int k = i & 63, col = i >> 6;
+        wlds[k * 32 + col] = make_float4(w2c[col * 64 + k],
+                                         w2c[(32 + col) * 64 + k],
+                                         w2g[col * 64 + k],
+                                         w2g[(32 + col) * 64 + k]);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+    const int64_t ntiles = (E + 31) >> 5;
+    const int64_t stride = (int64_t)gridDim.x * waves_per_block;
+    for (int64_t tile = blockIdx.x * (int64_t)waves_per_block + wave;
+         tile < ntiles; tile += stride) {
+        const int64_t base = tile << 5;
+        // opaque copy per tile, as in k_edge_mlp_64x128: keeps the
+        // per-register row offsets from being hoisted and spilled
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int c = lane_t & 31, h = lane_t >> 5;
+        const float4* bl = wlds + (4 * h) * 32 + c;
+        const int64_t r = base + c;
+        const bool live = r < E;
+        const int64_t off = r * 64 + 4 * h;
+        float dcv[32], dgv[32];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) dcv[q] = dgv[q] = 0.0f;
+        // ONE predicate around the whole A phase: lanes of rows >= E load
+        // and store nothing and feed zeros to the MFMAs.  (A predicate on
+        // each dw store instead splits the phase into 16 basic blocks and
+        // the register allocator then spills 47 VGPRs.)
+        if (live)
+            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, dcv, dgv);
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[cb][q] = 0.0f;
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl[(8 * i + t) * 32];   // k = 8i + 4h + t
+                const float ac = dcv[4 * i + t], ag = dgv[4 * i + t];
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, b.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, b.y, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(ag, b.z, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(ag, b.w, acc[3], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        if (base + 32 <= E)
+            mlp_tail_epilogue<true>(acc, z, dz, base, E, c, h);
+        else
+            mlp_tail_epilogue<false>(acc, z, dz, base, E, c, h);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GPU cell-list neighbor search (diagonal lattice, full PBC, min-image via
 // cell wrap).  fp64 math replicates the CPU builder's decisions exactly.
 // One thread per CENTER atom; center = dst so emission order is already
@@ -1438,6 +1663,31 @@ int dm_gated_combine_bwd_f32(const float* go, const float* c, const float* g,
     hipStream_t s = (hipStream_t)stream;
     k_gated_combine_bwd<<<nblocks(total, BLOCK), BLOCK, 0, s>>>(
         go, c, g, w, dc, dg, dw, total);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
+                              const float* w, const float* z,
+                              const float* w2c, const float* w2g, float* dz,
+                              float* dw, int64_t E, int64_t d,
+                              uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64) {
+        g_err = "gated_mlp_tail_bwd fused kernel is compiled for d=64";
+        return -1;
+    }
+    if ((w == nullptr) != (dw == nullptr)) {
+        g_err = "gated_mlp_tail_bwd: w and dw must be given together";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    if (w)
+        k_gated_mlp_tail_bwd<true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, c, g, w, z, w2c, w2g, dz, dw, E);
+    else
+        k_gated_mlp_tail_bwd<false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
     DM_CHECK_LAUNCH();
     return 0;
 }

@@ -57,6 +57,10 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_gated_combine_bwd_f32.restype = c_int32
         lib.dm_gated_combine_bwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                  c_int64, c_uint64]
+        lib.dm_gated_mlp_tail_bwd_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_bwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
+                                                  fp, fp, c_int64, c_int64,
+                                                  c_uint64]
         lib.dm_mace_tp_fwd_f32.restype = c_int32
         lib.dm_mace_tp_fwd_f32.argtypes = [fp, fp, fp, fp, ip, fp, c_int32,
                                            fp, fp, fp, fp, c_int64, c_int32,
@@ -527,6 +531,72 @@ class _GatedCombinePacked(torch.autograd.Function):
         return dcg, dw, (go if ctx.has_base else None)
 
 
+def raw_mlp_tail_bwd(go, cg, w, z, w2):
+    """(dz, dw) of one gated MLP's tail in ONE kernel: the reverse of
+    out = base + silu(cg[0]) * sigmoid(cg[1]) * w with cg = the second layer
+    over silu(z).  go [E,d], cg [2,E,d] packed, w [E,d] or None, z [E,2d],
+    w2 [2,d,d] (input x output per half).  d must be 64."""
+    _chk_f32(go, cg, w, z, w2)
+    E, d = go.shape
+    assert cg.shape == (2, E, d) and z.shape == (E, 2 * d)
+    assert w2.shape == (2, d, d) and (w is None or w.shape == (E, d))
+    half = E * d
+    dz = torch.empty_like(z)
+    dw = torch.empty_like(w) if w is not None else None
+    _check(hip_lib().dm_gated_mlp_tail_bwd_f32(
+        _fp(go), ctypes.cast(cg.data_ptr(), POINTER(c_float)),
+        ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
+        _fp(w) if w is not None else None, _fp(z),
+        ctypes.cast(w2.data_ptr(), POINTER(c_float)),
+        ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
+        _fp(dz), _fp(dw) if dw is not None else None, E, d, _stream()),
+        "dm_gated_mlp_tail_bwd_f32")
+    return dz, dw
+
+
+class _GatedMlpTail(torch.autograd.Function):
+    """Everything of a gated MLP after its first layer, as one node:
+    out = base + silu(c) * sigmoid(g) * w with cg = baddbmm(b2, h halves,
+    w2).  The forward is the baddbmm and dm_gated_combine_fwd_f32 of
+    chgnet._SecondLayer + _GatedCombinePacked; the backward is the single
+    dm_gated_mlp_tail_bwd_f32 launch, which goes from go to dz without
+    writing dcg or dh.
+
+    Contract: z and h are the two outputs of ONE first-layer call
+    (_EdgeMlp3/4, _GatherAdd3/4), so h == silu(z).  The gradient is then
+    returned on z (dz = dh * silu'(z)) and None on h; the producer's
+    backward takes go_z as dz when go_h is None.  Passing an h that is not
+    silu(z) of the given z gives wrong gradients: HipOps.mlp_tail checks
+    that both come from the same autograd node.  w2/b2 are frozen packs
+    (no weight grads)."""
+
+    @staticmethod
+    def forward(ctx, z, h, w2, b2, w, base):
+        _chk_f32(z, h, w2, w, base)
+        d = w2.shape[1]
+        assert z.shape == h.shape and z.shape[1] == 2 * d
+        assert not w2.requires_grad and not b2.requires_grad
+        cg = torch.baddbmm(b2, h.view(-1, 2, d).transpose(0, 1), w2)
+        half = cg.shape[1] * d
+        out = torch.empty(cg.shape[1], d, dtype=cg.dtype, device=cg.device)
+        _check(hip_lib().dm_gated_combine_fwd_f32(
+            ctypes.cast(cg.data_ptr(), POINTER(c_float)),
+            ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
+            _fp(w) if w is not None else None,
+            _fp(base) if base is not None else None, _fp(out), half,
+            _stream()), "dm_gated_combine_fwd_f32")
+        ctx.save_for_backward(cg, z, w2, w)
+        ctx.has_base = base is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        cg, z, w2, w = ctx.saved_tensors
+        go = go.contiguous()
+        dz, dw = raw_mlp_tail_bwd(go, cg, w, z, w2)
+        return dz, None, None, None, dw, (go if ctx.has_base else None)
+
+
 class HipOps:
     """Product ops backend (see ops_base.OpsBackend)."""
 
@@ -538,30 +608,52 @@ class HipOps:
                                "for its deterministic backward")
         return _Gather.apply(x.contiguous(), idx, csr[0], csr[1])
 
+    # The *_zh forms return (z, silu(z)) of one first-layer call, the pair
+    # mlp_tail takes; the *_act forms return silu(z) alone.
+
+    def gather_add3_zh(self, zs, zd, ze, pd):
+        return _GatherAdd3.apply(zs.contiguous(), zd.contiguous(),
+                                 ze.contiguous(), pd.src, pd.dst,
+                                 pd.src_perm, pd.src_row_ptr, pd.row_ptr)
+
     def gather_add3_act(self, zs, zd, ze, pd):
         """silu(zs[src] + zd[dst] + ze), silu fused into the gather kernel."""
-        _z, h = _GatherAdd3.apply(zs.contiguous(), zd.contiguous(),
-                                  ze.contiguous(), pd.src, pd.dst,
-                                  pd.src_perm, pd.src_row_ptr, pd.row_ptr)
-        return h
+        return self.gather_add3_zh(zs, zd, ze, pd)[1]
+
+    def edge_mlp3_zh(self, erow, wt, bias, zs, zd, pd):
+        return _EdgeMlp3.apply(erow.contiguous(), wt, bias, zs.contiguous(),
+                               zd.contiguous(), pd.src, pd.dst, pd.src_perm,
+                               pd.src_row_ptr, pd.row_ptr)
 
     def edge_mlp3_act(self, erow, wt, bias, zs, zd, pd):
         """silu(erow @ wt + bias + zs[src] + zd[dst]) fused in one kernel
         (wt = first-layer weight.T, [64,128] only)."""
-        _z, h = _EdgeMlp3.apply(erow.contiguous(), wt, bias, zs.contiguous(),
-                                zd.contiguous(), pd.src, pd.dst, pd.src_perm,
-                                pd.src_row_ptr, pd.row_ptr)
-        return h
+        return self.edge_mlp3_zh(erow, wt, bias, zs, zd, pd)[1]
+
+    def edge_mlp4_zh(self, arow, wt, bias, z1, z2, zv, pd):
+        return _EdgeMlp4.apply(arow.contiguous(), wt, bias, z1.contiguous(),
+                               z2.contiguous(), zv.contiguous(), pd)
 
     def edge_mlp4_act(self, arow, wt, bias, z1, z2, zv, pd):
-        _z, h = _EdgeMlp4.apply(arow.contiguous(), wt, bias, z1.contiguous(),
-                                z2.contiguous(), zv.contiguous(), pd)
-        return h
+        return self.edge_mlp4_zh(arow, wt, bias, z1, z2, zv, pd)[1]
+
+    def gather_add4_zh(self, z1, z2, za, zv, pd):
+        return _GatherAdd4.apply(z1.contiguous(), z2.contiguous(),
+                                 za.contiguous(), zv.contiguous(), pd)
 
     def gather_add4_act(self, z1, z2, za, zv, pd):
-        _z, h = _GatherAdd4.apply(z1.contiguous(), z2.contiguous(),
-                                  za.contiguous(), zv.contiguous(), pd)
-        return h
+        return self.gather_add4_zh(z1, z2, za, zv, pd)[1]
+
+    def mlp_tail(self, z, h, w2, b2, w=None, base=None):
+        """base + silu(c) * sigmoid(g) * w over cg = second layer of h, with
+        the one-kernel reverse pass (_GatedMlpTail).  (z, h) must be the
+        pair returned by ONE *_zh call of a grad-recording pass."""
+        assert z.grad_fn is not None and z.grad_fn is h.grad_fn, \
+            "mlp_tail: z and h must be the outputs of one first-layer call"
+        assert z.shape == h.shape and w2.shape[1] * 2 == z.shape[1]
+        return _GatedMlpTail.apply(
+            z, h, w2, b2, w.contiguous() if w is not None else None,
+            base.contiguous() if base is not None else None)
 
     def scatter_edges(self, msg, pd, base=None):
         return _SegSum.apply(msg, pd.dst, pd.row_ptr, pd.n_atoms, base)
@@ -617,6 +709,11 @@ class HipOps:
 
     def r_silu_bwd(self, go_h, z):
         return raw_silu_bwd(go_h.contiguous(), None, z)
+
+    def r_mlp_tail_bwd(self, go, cg, w, z, w2):
+        """(dz, dw): r_combine_bwd + second-layer reverse + r_silu_bwd in
+        one kernel (d = 64 only)."""
+        return raw_mlp_tail_bwd(go, cg, w, z, w2)
 
     def r_gather_dst(self, x, pd):
         return raw_gather(x.contiguous(), pd.dst)

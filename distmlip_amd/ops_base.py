@@ -26,6 +26,15 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                          -> the 3-gather line-graph form
     scatter_edges(msg, pd, base)         -> base + segment-sum of the
                                             dst-sorted msg rows per node
+    mlp_tail(z, h, w2, b2, w, base)      -> base + silu(c)*sigmoid(g)*w over
+                                            cg = second layer of h, with a
+                                            one-kernel reverse pass that
+                                            returns its gradient on z.
+                                            OPTIONAL (HipOps, d = 64); (z, h)
+                                            are the pair of ONE *_zh call
+                                            (gather_add3_zh, edge_mlp3_zh,
+                                            ...: the *_act forms that also
+                                            return z)
 
   RAW primitives (prefix r_): NON-differentiable single kernels used by
   the hand-sequenced conv backward (distmlip_amd.conv._AtomConvFn),
@@ -37,6 +46,12 @@ the permutation CSRs the graph builder emits; `csr` is an optional
     r_combine_fwd(cg, w, base)           -> base + silu(cg0)*sigmoid(cg1)*w
     r_combine_bwd(go, cg, w)             -> (dcg [2,*,D], dw)
     r_silu_bwd(go_h, z)                  -> go_h * silu'(z)
+    r_mlp_tail_bwd(go, cg, w, z, w2)     -> (dz, dw): r_combine_bwd, the
+                                            second layer's reverse GEMMs
+                                            and r_silu_bwd as one kernel.
+                                            OPTIONAL (HipOps, d = 64): conv
+                                            falls back to the three calls
+                                            where a backend lacks it
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

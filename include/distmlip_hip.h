@@ -99,6 +99,24 @@ int dm_gated_combine_bwd_f32(const float* go, const float* c, const float* g,
                              const float* w, float* dc, float* dg, float* dw,
                              int64_t total, uint64_t stream);
 
+/* Fused reverse tail of one gated MLP, from the gradient go [E,d] of
+ *   out = base + silu(c) * sigmoid(g) * (w?w:1)
+ * to the gradient dz [E,2d] of the first layer's pre-activation z, where
+ * c = h[:, :d] @ w2c, g = h[:, d:] @ w2g and h = silu(z):
+ *   dc = go*w*sig(g)*silu'(c)       dg = go*w*silu(c)*sig(g)*(1-sig(g))
+ *   dw = go*silu(c)*sig(g)
+ *   dz = [dc @ w2c^T | dg @ w2g^T] * silu'(z)
+ * One kernel in place of dm_gated_combine_bwd_f32 + two GEMMs +
+ * dm_silu_bwd_f32; dc, dg and dh never reach memory.  c and g are the two
+ * halves of a packed [2,E,d] buffer (or any two [E,d] arrays); w2c, w2g are
+ * [d,d] row-major, input x output.  w and dw are both NULL or both given.
+ * Compiled for d = 64: any other d returns an error and launches nothing. */
+int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
+                              const float* w, const float* z,
+                              const float* w2c, const float* w2g, float* dz,
+                              float* dw, int64_t E, int64_t d,
+                              uint64_t stream);
+
 /* Fused edge geometry + radial basis (replaces the torch chain for
  * chgnet.py:96-124): per local edge e,
  *   bv[e]  = pos[dst[e]] + offshift[e] - pos[src[e]]
