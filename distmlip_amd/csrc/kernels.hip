@@ -1514,6 +1514,11 @@ __global__ void k_rot_dD(const float* __restrict__ go,
 }
 
 
+// The library's other translation units (tensornet.hip) report through the
+// same per-thread message dm_hip_last_error() returns.  Not exported.
+__attribute__((visibility("hidden")))
+void dm_set_last_error(const char* msg) { g_err = msg; }
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------

@@ -87,6 +87,16 @@ def hip_lib() -> ctypes.CDLL:
                                            ip, fp, c_int32, fp, fp, fp, fp,
                                            c_int64, c_int32, c_int32,
                                            c_int32, c_uint64]
+        # TensorNet message pass (distmlip_amd/tensornet_ops.py)
+        lib.dm_tn_msg_fwd_f32.restype = c_int32
+        lib.dm_tn_msg_fwd_f32.argtypes = [fp, fp, ip, ip, fp, c_int64,
+                                          c_int32, c_uint64]
+        lib.dm_tn_msg_bwd_edge_f32.restype = c_int32
+        lib.dm_tn_msg_bwd_edge_f32.argtypes = [fp, fp, ip, ip, fp, c_int64,
+                                               c_int32, c_uint64]
+        lib.dm_tn_msg_bwd_node_f32.restype = c_int32
+        lib.dm_tn_msg_bwd_node_f32.argtypes = [fp, fp, ip, ip, ip, fp,
+                                               c_int64, c_int32, c_uint64]
         cf = ctypes.c_float
         lib.dm_edge_geom_rbf_fwd_f32.restype = c_int32
         lib.dm_edge_geom_rbf_fwd_f32.argtypes = [fp, ip, ip, fp, fp, cf,

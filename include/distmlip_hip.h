@@ -254,6 +254,43 @@ int dm_rot_dD_f32(const float* go, const float* h, const int32_t* idx,
                   int32_t trans, float* dD, int64_t E, int32_t C,
                   uint64_t stream);
 
+/* TensorNet tensor message pass, fused per node.  Replaces the matgl
+ * TensorNetInteraction message step the reference's TensorNet_Dist delegates
+ * to (implementations/matgl/models/tensornet.py, the per-layer loop around
+ * atom_transfer): node tensors are stored component-major, Y [N,9,C] with
+ * row 3a+b, the per-edge radial weights f [E,3,C] with k in {I, A, S}, and
+ * P_k is the projection of a 3x3 tensor onto its isotropic (tr/3 * 1),
+ * antisymmetric ((T - T^T)/2) or symmetric-traceless part, per channel.
+ * Edges are DST-SORTED (builder layout): row_ptr [N+1] is the dst CSR,
+ * (src_perm, src_row_ptr) the src permutation CSR.
+ *
+ *   fwd:      M[i,:,c]  = sum_{e in [row_ptr[i], row_ptr[i+1])}
+ *                         sum_k f[e,k,c] * P_k(Y[src[e],:,c])
+ *   bwd_edge: df[e,k,c] = < G[dst(e),:,c], P_k(Y[src[e],:,c]) >,  G = dL/dM,
+ *             dst(e) = the row of the dst CSR that holds e
+ *   bwd_node: dY[j,:,c] = sum_{p in [src_row_ptr[j], src_row_ptr[j+1])}
+ *                         sum_k f[e,k,c] * P_k(G[dst[e],:,c]),  e = src_perm[p]
+ *   (the projections are self-adjoint under the Frobenius product, so the
+ *   reverse needs no transposed form).
+ *
+ * One wave per (node, 64-channel block), lane = channel, nine accumulators
+ * in registers: no [E,9,C] intermediate, no atomics, each row summed in CSR
+ * order, so results are bit-identical from run to run.  A row without edges
+ * writes zeros (fwd, bwd_node) or nothing (bwd_edge has no rows to write).
+ * N == 0 returns 0 with no launch; a graph without edges (row_ptr all zero)
+ * reads row_ptr only, so Y, f, src may then be NULL.  C must be a positive
+ * multiple of 64: anything else returns nonzero and launches nothing. */
+int dm_tn_msg_fwd_f32(const float* Y, const float* f, const int32_t* src,
+                      const int32_t* row_ptr, float* M, int64_t N, int32_t C,
+                      uint64_t stream);
+int dm_tn_msg_bwd_edge_f32(const float* G, const float* Y, const int32_t* src,
+                           const int32_t* row_ptr, float* df, int64_t N,
+                           int32_t C, uint64_t stream);
+int dm_tn_msg_bwd_node_f32(const float* G, const float* f, const int32_t* dst,
+                           const int32_t* src_perm,
+                           const int32_t* src_row_ptr, float* dY, int64_t N,
+                           int32_t C, uint64_t stream);
+
 const char* dm_hip_last_error(void);
 
 #ifdef __cplusplus
