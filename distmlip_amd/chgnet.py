@@ -151,6 +151,24 @@ def _use_fused_tail(ops, d: int, wcg) -> bool:
             and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1")
 
 
+def _use_fused_tail_fwd(ops, d: int, wcg, h, w, base) -> bool:
+    """Fused forward tail policy for passes that record nothing
+    (ops.mlp_tail_act: second layer + combine in one kernel, no cg
+    transient): on for d = 64 with frozen weights on a backend that has it,
+    when no input of the tail needs a gradient (energy-only inference, any
+    torch.no_grad pass).  Recording passes reach the same kernel in its
+    cg-keeping form through ops.mlp_tail; that includes the outer forward of
+    a non-reentrant checkpoint, which records like any other pass and has
+    its saves dropped by the checkpoint's hooks.  DM_NO_FUSED_MLP_FWD=1
+    restores baddbmm + dm_gated_combine_fwd_f32 in both, for A/B runs in one
+    build."""
+    if not (d == 64 and not wcg.requires_grad and hasattr(ops, "mlp_tail_act")
+            and os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1"):
+        return False
+    return not (torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (h, w, base)))
+
+
 def gated_mlp_split3(mlp: GatedMLP, v, e, pd, ops, d: int, w=None, base=None):
     """GatedMLP over cat(v[src], v[dst], e) via split-linear + one 2h-wide
     gather_add3, finished by the fused gated-combine epilogue:
@@ -170,6 +188,8 @@ def gated_mlp_split3(mlp: GatedMLP, v, e, pd, ops, d: int, w=None, base=None):
     z, h = zh if tail else (None, zh)
     if tail and h.requires_grad:
         return ops.mlp_tail(z, h, w2, b2, w, base)
+    if _use_fused_tail_fwd(ops, d, wcg, h, w, base):
+        return ops.mlp_tail_act(h, w2, b2, w, base)
     cg = _second_layer_packed(h, w2, b2, d)
     return ops.gated_combine_packed(cg, w, base)
 
@@ -192,6 +212,8 @@ def gated_mlp_split4(mlp: GatedMLP, n, a, v, pd, ops, d: int, w=None,
     z, h = zh if tail else (None, zh)
     if tail and h.requires_grad:
         return ops.mlp_tail(z, h, w2p, b2p, w, base)
+    if _use_fused_tail_fwd(ops, d, wcg, h, w, base):
+        return ops.mlp_tail_act(h, w2p, b2p, w, base)
     cg = _second_layer_packed(h, w2p, b2p, d)
     return ops.gated_combine_packed(cg, w, base)
 

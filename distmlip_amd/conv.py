@@ -52,6 +52,32 @@ def _mlp_tail_bwd(ops, go, cg, w, z, w2, d):
     return ops.r_silu_bwd(_second_bwd(dcg, w2, d), z), dw
 
 
+def _fused_tail_fwd(ops, d, name):
+    return (d == 64 and hasattr(ops, name)
+            and os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1")
+
+
+def _mlp_tail_fwd(ops, h, w2, b2, w, base, d):
+    """(cg, out) with cg = the second layer over h and out =
+    r_combine_fwd(cg, w, base): one kernel where the backend has
+    r_mlp_tail_fwd (d = 64), else baddbmm + combine.  DM_NO_FUSED_MLP_FWD=1
+    forces the latter for A/B runs."""
+    if _fused_tail_fwd(ops, d, "r_mlp_tail_fwd"):
+        return ops.r_mlp_tail_fwd(h, w2, b2, w, base)
+    cg = _second_fwd(h, w2, b2, d)
+    return cg, ops.r_combine_fwd(cg, w, base)
+
+
+def _mlp_tail_act(ops, h, w2, b2, w, base, d):
+    """out of _mlp_tail_fwd alone, for the save-nothing forwards: no cg is
+    written where the backend has mlp_tail_act."""
+    records = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (h, w, base))
+    if not records and _fused_tail_fwd(ops, d, "mlp_tail_act"):
+        return ops.mlp_tail_act(h, w2, b2, w, base)
+    return ops.gated_combine_packed(_second_fwd(h, w2, b2, d), w, base)
+
+
 def _unpack_edge(packs, d):
     wcg, bcg, w2, b2 = packs
     return wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:], bcg, w2, b2
@@ -64,12 +90,10 @@ def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d):
     ws2, wd2, we2, bcg2, w22, b22 = _unpack_edge(packs_node, d)
     z1, h1 = ops.r_gather_add3(v @ ws1.t(), v @ wd1.t(),
                                torch.addmm(bcg1, e, we1.t()), pd)
-    cg1 = _second_fwd(h1, w21, b21, d)
-    e2 = ops.r_combine_fwd(cg1, wbb, e)
+    cg1, e2 = _mlp_tail_fwd(ops, h1, w21, b21, wbb, e, d)
     z2, h2 = ops.r_gather_add3(v @ ws2.t(), v @ wd2.t(),
                                torch.addmm(bcg2, e2, we2.t()), pd)
-    cg2 = _second_fwd(h2, w22, b22, d)
-    msg = ops.r_combine_fwd(cg2, wab, None)
+    cg2, msg = _mlp_tail_fwd(ops, h2, w22, b22, wab, None, d)
     v2 = ops.r_seg_dst(msg, pd, base=v)
     return v2, e2, (z1, cg1, z2, cg2)
 
@@ -170,8 +194,7 @@ def bond_fwd(ops, pd, n, a, v, w3, packs, d, mask_l=None):
         wl = wl * mask_l
     z, h = ops.r_gather_add4(n @ w1.t(), n @ wn2.t(),
                              torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
-    cg = _second_fwd(h, w2, b2, d)
-    msg = ops.r_combine_fwd(cg, wl, None)
+    cg, msg = _mlp_tail_fwd(ops, h, w2, b2, wl, None, d)
     n2 = ops.r_seg_ldst(msg, pd, base=n)
     return n2, (z, cg, wl)
 
@@ -217,8 +240,7 @@ def angle_fwd(ops, pd, n, a, v, packs, d):
                        wcg[:, 3 * d:])
     z, h = ops.r_gather_add4(n @ w1.t(), n @ wn2.t(),
                              torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
-    cg = _second_fwd(h, w2, b2, d)
-    a2 = ops.r_combine_fwd(cg, None, a)
+    cg, a2 = _mlp_tail_fwd(ops, h, w2, b2, None, a, d)
     return a2, (z, cg)
 
 
@@ -291,7 +313,7 @@ def _lean_atom(ops, pd, v, e, wbb, wab, pe, pn, d):
         h1 = ops.gather_add3_act(v @ ws1.t(), v @ wd1.t(),
                                  torch.addmm(bcg1, e, wcg1[:, 2 * d:].t()),
                                  pd)
-    e2 = ops.gated_combine_packed(_second_fwd(h1, w21, b21, d), wbb, e)
+    e2 = _mlp_tail_act(ops, h1, w21, b21, wbb, e, d)
     if d == 64 and hasattr(ops, "edge_mlp3_act"):
         h2 = ops.edge_mlp3_act(e2, fusedT2, bcg2, v @ ws2.t(), v @ wd2.t(),
                                pd)
@@ -299,7 +321,7 @@ def _lean_atom(ops, pd, v, e, wbb, wab, pe, pn, d):
         h2 = ops.gather_add3_act(v @ ws2.t(), v @ wd2.t(),
                                  torch.addmm(bcg2, e2, wcg2[:, 2 * d:].t()),
                                  pd)
-    msg = ops.gated_combine_packed(_second_fwd(h2, w22, b22, d), wab)
+    msg = _mlp_tail_act(ops, h2, w22, b22, wab, None, d)
     return ops.scatter_edges(msg, pd, base=v), e2
 
 
@@ -314,7 +336,7 @@ def _lean_bond(ops, pd, n, a, v, w3, pb, d):
         h = ops.gather_add4_act(n @ w1.t(), n @ wn2.t(),
                                 torch.addmm(bcg, a, wcg[:, 2 * d:3 * d].t()),
                                 v @ wv.t(), pd)
-    msg = ops.gated_combine_packed(_second_fwd(h, w2, b2, d), wl)
+    msg = _mlp_tail_act(ops, h, w2, b2, wl, None, d)
     return ops.scatter_lines(msg, pd, base=n)
 
 
@@ -328,7 +350,7 @@ def _lean_angle(ops, pd, n, a, v, pa, d):
         h = ops.gather_add4_act(n @ w1.t(), n @ wn2.t(),
                                 torch.addmm(bcg, a, wcg[:, 2 * d:3 * d].t()),
                                 v @ wv.t(), pd)
-    return ops.gated_combine_packed(_second_fwd(h, w2, b2, d), None, a)
+    return _mlp_tail_act(ops, h, w2, b2, None, a, d)
 
 
 def _edge_to_bond(pd, n, e):
@@ -543,7 +565,7 @@ def _lean_edge_update(ops, pd, v, e, wbb, pe, d):
         h1 = ops.gather_add3_act(v @ ws1.t(), v @ wd1.t(),
                                  torch.addmm(bcg1, e, wcg1[:, 2 * d:].t()),
                                  pd)
-    return ops.gated_combine_packed(_second_fwd(h1, w21, b21, d), wbb, e)
+    return _mlp_tail_act(ops, h1, w21, b21, wbb, e, d)
 
 
 def atom_bwd_recompute(ops, pd, v_in, e_in, wbb, wab, pe, pn, d,
@@ -563,6 +585,8 @@ def atom_bwd_recompute(ops, pd, v_in, e_in, wbb, wab, pe, pn, d,
         z2, h2 = ops.r_gather_add3(v_in @ ws2.t(), v_in @ wd2.t(),
                                    torch.addmm(bcg2, e2, we2.t()), pd)
         del e2
+        # cg only: the reverse below needs no out, so the GEMM alone
+        # (4 [E,d] units of traffic) is less work than the fused tail (5+)
         cg2 = _second_fwd(h2, w22, pn[3], d)
         del h2
         dmsg = ops.r_gather_dst(go_v2, pd)

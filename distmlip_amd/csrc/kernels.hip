@@ -913,6 +913,200 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]
 }
 
 // ---------------------------------------------------------------------------
+// Fused forward tail of one gated MLP (d = 64): second layer + combine,
+//   c = h[:, :64] @ w2c + b2c      g = h[:, 64:] @ w2g + b2g
+//   out = base + silu(c) * sigmoid(g) * w
+// in one pass over h.  It replaces the rocBLAS baddbmm + k_gated_combine_fwd:
+// c|g ([2,E,64]) are written only when a reverse pass will read them (KEEP)
+// and are never read back.  The scalar expression is k_gated_combine_fwd's
+// (exact expf and division), and does not depend on KEEP: out is the same
+// bit for bit with and without the c|g stores.
+//
+// Skeleton of k_edge_mlp_64x128 / k_gated_mlp_tail_bwd: one wave owns 32
+// rows and 4 accumulators (v_mfma_f32_32x32x2_f32, starting at 0), 4 waves
+// per block, grid capped by edge_mlp_blocks.
+//  * Accumulators 0,1 are c columns col, 32+col; 2,3 are g columns col,
+//    32+col.
+//  * B operand: LDS float4 [k][col] = (w2c[k][col], w2c[k][32+col],
+//    w2g[k][col], w2g[k][32+col]), 32 KB; w2 is [in, out] row-major, so the
+//    staging is a straight regrouping and one ds_read_b128 per k-step feeds
+//    the four MFMAs of that step.
+//  * A operand without LDS and without a transposition: h is row-major in
+//    memory, and lane (r = lane&31, hh = lane>>5) reads its own row at
+//    floats [8i+4hh, 8i+4hh+4) of the low and of the high half, 16 float4s
+//    all issued before the first MFMA.  Step 4i+t contracts k = 8i+4hh+t;
+//    accumulators 0,1 take the low-half value, 2,3 the high-half value.
+//  * Epilogue in the accumulator layout (col = lane&31, row = (reg&3) +
+//    8*(reg>>2) + 4*(lane>>5)): c and g of one (row, col) sit in the same
+//    lane, so the combine is lane-local.  b2 is added here and not folded
+//    into the accumulator init, for the reason given at k_edge_mlp_64x128.
+//    w and base are loaded 8 rows at a time, all loads of a batch in flight
+//    before any is used.
+//  * Tails: loads of rows >= E are clamped to row E-1, stores predicated.
+//    All row offsets are 64-bit.
+// Resources (hipcc -O3, gfx950, kernel-resource-usage remarks), all eight
+// <KEEP, HAS_W, HAS_BASE> variants: 152 VGPR, 0 AGPR, 31-68 SGPR, 32 KB LDS,
+// 3 waves/SIMD, no scratch.
+// Measured at si1m (rocprofv3 kernel trace, 3 steps; every launch there is a
+// KEEP one): at E = 46M rows with w and base, 24 launches, 13.8 ms average
+// (13.65-14.43); with w alone 12.85 ms (12.68-12.98); at L = 12M rows 3.8
+// ms.  The chain it replaces took, in the parent's trace of the same
+// session, 13.9 (rocBLAS MT64x256x16) + 11.8 / 8.85 (k_gated_combine_fwd
+// with w and base / with one of them) ms at 46M rows and 4.15 + 2.55 at 12M.
+// Algorithmic bytes at 46M rows, KEEP with w and base: 82.4 GB = 13.1 ms at
+// 6.29 TB/s.
+// Stand-alone on random inputs, 46M rows (median of 5; chain 18.5 + 12.7 ms
+// there):    w+base   w      base   neither
+//   KEEP     14.53    13.44  13.46  -
+//   no KEEP  12.49    11.86  11.77  10.80   (10.8 ms: 35 GB at 3.3 TB/s, the
+//                                            MFMA-issue bound of this shape)
+// Tried (same stand-alone run, KEEP w+base / no-KEEP w+base / no-KEEP
+// neither):
+//  * epilogue batches of 4 rows instead of 8: 14.67 / 12.66 / 10.87 ms, 152
+//    VGPR.  8 kept.
+//  * A loads in two chunks of 4 slices with the MFMAs of a chunk in between
+//    (as TAIL_CHUNK does in the reverse kernel): 122-139 VGPR, 4 waves/SIMD
+//    in six variants, 14.63 / 12.54 / 11.06 ms.  No gain; all 16 loads up
+//    front kept.
+//  * leaving the epilogue's r*w + base to the compiler (one fma): out then
+//    differs from k_gated_combine_fwd's in the last bit.  The stand-alone
+//    numbers above were taken with that version, the si1m ones with this.
+// ---------------------------------------------------------------------------
+template <bool KEEP, bool HAS_W, bool HAS_BASE, bool FULL>
+__device__ __forceinline__ void mlp_tail_fwd_epilogue(
+        const f32x16 (&acc)[4], const float4 bcol,
+        const float* __restrict__ w, const float* __restrict__ bs,
+        float* __restrict__ cout, float* __restrict__ gout,
+        float* __restrict__ out, int64_t base, int64_t E, int c, int h) {
+    constexpr int G = 8;
+#pragma unroll
+    for (int rb = 0; rb < 16; rb += G) {
+        float wv[G][2], bv[G][2];
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t row = base + rl;
+            const int64_t lrow = (FULL || row < E) ? row : E - 1;
+            if (HAS_W) {
+                wv[t][0] = w[lrow * 64 + c];
+                wv[t][1] = w[lrow * 64 + 32 + c];
+            }
+            if (HAS_BASE) {
+                bv[t][0] = bs[lrow * 64 + c];
+                bv[t][1] = bs[lrow * 64 + 32 + c];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t row = base + rl;
+            const float cv[2] = {acc[0][r] + bcol.x, acc[1][r] + bcol.y};
+            const float gv[2] = {acc[2][r] + bcol.z, acc[3][r] + bcol.w};
+            if (FULL || row < E) {
+                const int64_t o = row * 64 + c;
+                if (KEEP) {
+                    cout[o] = cv[0]; cout[o + 32] = cv[1];
+                    gout[o] = gv[0]; gout[o + 32] = gv[1];
+                }
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    // k_gated_combine_fwd rounds each product and the
+                    // +base separately (its w and base branches keep them
+                    // from being contracted to an fma): the same here, so
+                    // out equals that kernel's over the same c|g bit for
+                    // bit
+#pragma clang fp contract(off)
+                    float x = cv[q] * sigf(cv[q]) * sigf(gv[q]);
+                    if (HAS_W) x *= wv[t][q];
+                    if (HAS_BASE) x += bv[t][q];
+                    out[o + 32 * q] = x;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one row at a time
+        }
+    }
+}
+
+template <bool KEEP, bool HAS_W, bool HAS_BASE>
+__global__ __launch_bounds__(256, 3)
+void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
+                          const float* __restrict__ w2c,   // [64,64] in x out
+                          const float* __restrict__ w2g,
+                          const float* __restrict__ b2c,   // [64]
+                          const float* __restrict__ b2g,
+                          const float* __restrict__ w,     // [E,64], HAS_W
+                          const float* __restrict__ bs,    // [E,64], HAS_BASE
+                          float* __restrict__ cout,        // [E,64], KEEP
+                          float* __restrict__ gout,        // [E,64], KEEP
+                          float* __restrict__ out,         // [E,64]
+                          int64_t E) {
+    __shared__ float4 wlds[64 * 32];
+    for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
+        const int k = i >> 5, col = i & 31;
+        wlds[i] = make_float4(w2c[k * 64 + col], w2c[k * 64 + 32 + col],
+                              w2g[k * 64 + col], w2g[k * 64 + 32 + col]);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int c0 = lane & 31;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+    const float4 bcol = make_float4(b2c[c0], b2c[32 + c0], b2g[c0],
+                                    b2g[32 + c0]);
+    const int64_t ntiles = (E + 31) >> 5;
+    const int64_t stride = (int64_t)gridDim.x * waves_per_block;
+    for (int64_t tile = blockIdx.x * (int64_t)waves_per_block + wave;
+         tile < ntiles; tile += stride) {
+        const int64_t base = tile << 5;
+        // opaque copy per tile, as in k_edge_mlp_64x128: keeps the
+        // per-register row offsets from being hoisted and spilled
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int c = lane_t & 31, h = lane_t >> 5;
+        const float4* bl = wlds + (4 * h) * 32 + c;
+        const int64_t r = base + c;
+        const int64_t lrow = r < E ? r : E - 1;   // clamp, never read past E
+        const float4* ap = (const float4*)(hp + lrow * 128) + h;
+        float4 alo[8], ahi[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            alo[i] = ap[2 * i];
+            ahi[i] = ap[16 + 2 * i];
+        }
+        __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
+        f32x16 acc[4];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[cb][q] = 0.0f;
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float lo[4] = {alo[i].x, alo[i].y, alo[i].z, alo[i].w};
+            const float hi[4] = {ahi[i].x, ahi[i].y, ahi[i].z, ahi[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl[(8 * i + t) * 32];   // k = 8i + 4h + t
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(lo[t], b.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(lo[t], b.y, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi[t], b.z, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi[t], b.w, acc[3], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        if (base + 32 <= E)
+            mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, true>(
+                acc, bcol, w, bs, cout, gout, out, base, E, c, h);
+        else
+            mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, false>(
+                acc, bcol, w, bs, cout, gout, out, base, E, c, h);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GPU cell-list neighbor search (diagonal lattice, full PBC, min-image via
 // cell wrap).  fp64 math replicates the CPU builder's decisions exactly.
 // One thread per CENTER atom; center = dst so emission order is already
@@ -1514,6 +1708,23 @@ __global__ void k_rot_dD(const float* __restrict__ go,
 }
 
 
+// dm_gated_mlp_tail_fwd_f32's launch, by variant
+template <bool KEEP, bool HAS_W>
+static void launch_mlp_tail_fwd(const float* h, const float* w2c,
+                                const float* w2g, const float* b2c,
+                                const float* b2g, const float* w,
+                                const float* base, float* c_out, float* g_out,
+                                float* out, int64_t E, hipStream_t s) {
+    if (base)
+        k_gated_mlp_tail_fwd<KEEP, HAS_W, true>
+            <<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+                h, w2c, w2g, b2c, b2g, w, base, c_out, g_out, out, E);
+    else
+        k_gated_mlp_tail_fwd<KEEP, HAS_W, false>
+            <<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+                h, w2c, w2g, b2c, b2g, w, nullptr, c_out, g_out, out, E);
+}
+
 // The library's other translation units (tensornet.hip) report through the
 // same per-thread message dm_hip_last_error() returns.  Not exported.
 __attribute__((visibility("hidden")))
@@ -1693,6 +1904,38 @@ int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
     else
         k_gated_mlp_tail_bwd<false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
             go, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp_tail_fwd_f32(const float* h, const float* w2c,
+                              const float* w2g, const float* b2c,
+                              const float* b2g, const float* w,
+                              const float* base, float* c_out, float* g_out,
+                              float* out, int64_t E, int64_t d,
+                              uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64) {
+        g_err = "gated_mlp_tail_fwd fused kernel is compiled for d=64";
+        return -1;
+    }
+    if ((c_out == nullptr) != (g_out == nullptr)) {
+        g_err = "gated_mlp_tail_fwd: c_out and g_out must be given together";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    if (c_out) {
+        if (w) launch_mlp_tail_fwd<true, true>(h, w2c, w2g, b2c, b2g, w, base,
+                                               c_out, g_out, out, E, s);
+        else launch_mlp_tail_fwd<true, false>(h, w2c, w2g, b2c, b2g, nullptr,
+                                              base, c_out, g_out, out, E, s);
+    } else {
+        if (w) launch_mlp_tail_fwd<false, true>(h, w2c, w2g, b2c, b2g, w, base,
+                                                nullptr, nullptr, out, E, s);
+        else launch_mlp_tail_fwd<false, false>(h, w2c, w2g, b2c, b2g, nullptr,
+                                               base, nullptr, nullptr, out, E,
+                                               s);
+    }
     DM_CHECK_LAUNCH();
     return 0;
 }

@@ -13,6 +13,7 @@ device — there is no fallback.
 from __future__ import annotations
 
 import ctypes
+import os
 from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_uint64
 
 import torch
@@ -61,6 +62,10 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_gated_mlp_tail_bwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                   fp, fp, c_int64, c_int64,
                                                   c_uint64]
+        lib.dm_gated_mlp_tail_fwd_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_fwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
+                                                  fp, fp, fp, c_int64,
+                                                  c_int64, c_uint64]
         lib.dm_mace_tp_fwd_f32.restype = c_int32
         lib.dm_mace_tp_fwd_f32.argtypes = [fp, fp, fp, fp, ip, fp, c_int32,
                                            fp, fp, fp, fp, c_int64, c_int32,
@@ -564,11 +569,50 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2):
     return dz, dw
 
 
+def use_fused_tail_fwd() -> bool:
+    """Forward-tail kernel switch: DM_NO_FUSED_MLP_FWD=1 restores baddbmm +
+    dm_gated_combine_fwd_f32 everywhere, for A/B runs in one build."""
+    return os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1"
+
+
+def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
+    """(out, cg or None) of one gated MLP's tail in ONE kernel:
+    cg = baddbmm(b2, h halves, w2) and out = base + silu(cg[0]) *
+    sigmoid(cg[1]) * w.  h [E,2d], w2 [2,d,d] (input x output per half),
+    b2 [2,1,d], w and base [E,d] or None.  cg [2,E,d] packed is written and
+    returned only with keep_cg; out is the same bit for bit either way.
+    d must be 64."""
+    _chk_f32(h, w2, b2, w, base)
+    E, d = h.shape[0], w2.shape[1]
+    assert h.shape == (E, 2 * d) and w2.shape == (2, d, d)
+    assert b2.numel() == 2 * d
+    assert w is None or w.shape == (E, d)
+    assert base is None or base.shape == (E, d)
+    half = E * d
+    out = torch.empty(E, d, dtype=h.dtype, device=h.device)
+    cg = torch.empty(2, E, d, dtype=h.dtype, device=h.device) \
+        if keep_cg else None
+    _check(hip_lib().dm_gated_mlp_tail_fwd_f32(
+        _fp(h), ctypes.cast(w2.data_ptr(), POINTER(c_float)),
+        ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
+        ctypes.cast(b2.data_ptr(), POINTER(c_float)),
+        ctypes.cast(b2.data_ptr() + 4 * d, POINTER(c_float)),
+        _fp(w) if w is not None else None,
+        _fp(base) if base is not None else None,
+        ctypes.cast(cg.data_ptr(), POINTER(c_float)) if keep_cg else None,
+        ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float))
+        if keep_cg else None,
+        _fp(out), E, d, _stream()), "dm_gated_mlp_tail_fwd_f32")
+    return out, cg
+
+
 class _GatedMlpTail(torch.autograd.Function):
     """Everything of a gated MLP after its first layer, as one node:
     out = base + silu(c) * sigmoid(g) * w with cg = baddbmm(b2, h halves,
-    w2).  The forward is the baddbmm and dm_gated_combine_fwd_f32 of
-    chgnet._SecondLayer + _GatedCombinePacked; the backward is the single
+    w2).  The forward is the single dm_gated_mlp_tail_fwd_f32 launch, which
+    writes cg for the backward and never reads it back (with
+    DM_NO_FUSED_MLP_FWD=1: the baddbmm and dm_gated_combine_fwd_f32 of
+    chgnet._SecondLayer + _GatedCombinePacked); the backward is the single
     dm_gated_mlp_tail_bwd_f32 launch, which goes from go to dz without
     writing dcg or dh.
 
@@ -586,15 +630,19 @@ class _GatedMlpTail(torch.autograd.Function):
         d = w2.shape[1]
         assert z.shape == h.shape and z.shape[1] == 2 * d
         assert not w2.requires_grad and not b2.requires_grad
-        cg = torch.baddbmm(b2, h.view(-1, 2, d).transpose(0, 1), w2)
-        half = cg.shape[1] * d
-        out = torch.empty(cg.shape[1], d, dtype=cg.dtype, device=cg.device)
-        _check(hip_lib().dm_gated_combine_fwd_f32(
-            ctypes.cast(cg.data_ptr(), POINTER(c_float)),
-            ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
-            _fp(w) if w is not None else None,
-            _fp(base) if base is not None else None, _fp(out), half,
-            _stream()), "dm_gated_combine_fwd_f32")
+        if d == 64 and use_fused_tail_fwd():
+            out, cg = raw_mlp_tail_fwd(h, w2, b2, w, base, True)
+        else:
+            cg = torch.baddbmm(b2, h.view(-1, 2, d).transpose(0, 1), w2)
+            half = cg.shape[1] * d
+            out = torch.empty(cg.shape[1], d, dtype=cg.dtype,
+                              device=cg.device)
+            _check(hip_lib().dm_gated_combine_fwd_f32(
+                ctypes.cast(cg.data_ptr(), POINTER(c_float)),
+                ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
+                _fp(w) if w is not None else None,
+                _fp(base) if base is not None else None, _fp(out), half,
+                _stream()), "dm_gated_combine_fwd_f32")
         ctx.save_for_backward(cg, z, w2, w)
         ctx.has_base = base is not None
         return out
@@ -665,6 +713,19 @@ class HipOps:
             z, h, w2, b2, w.contiguous() if w is not None else None,
             base.contiguous() if base is not None else None)
 
+    def mlp_tail_act(self, h, w2, b2, w=None, base=None):
+        """mlp_tail's value for passes that record nothing (torch.no_grad
+        inference, the lean recompute forwards of conv.py): out only, no cg is
+        allocated or written.  Not differentiable: refused when an input
+        would need a gradient."""
+        assert not (torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (h, w, base))), \
+            "mlp_tail_act is the no-grad form; use mlp_tail"
+        return raw_mlp_tail_fwd(
+            h.contiguous(), w2, b2,
+            w.contiguous() if w is not None else None,
+            base.contiguous() if base is not None else None, False)[0]
+
     def scatter_edges(self, msg, pd, base=None):
         return _SegSum.apply(msg, pd.dst, pd.row_ptr, pd.n_atoms, base)
 
@@ -724,6 +785,12 @@ class HipOps:
         """(dz, dw): r_combine_bwd + second-layer reverse + r_silu_bwd in
         one kernel (d = 64 only)."""
         return raw_mlp_tail_bwd(go, cg, w, z, w2)
+
+    def r_mlp_tail_fwd(self, h, w2, b2, w, base):
+        """(cg, out): second layer + r_combine_fwd in one kernel (d = 64
+        only)."""
+        out, cg = raw_mlp_tail_fwd(h, w2, b2, w, base, True)
+        return cg, out
 
     def r_gather_dst(self, x, pd):
         return raw_gather(x.contiguous(), pd.dst)

@@ -35,6 +35,11 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             (gather_add3_zh, edge_mlp3_zh,
                                             ...: the *_act forms that also
                                             return z)
+    mlp_tail_act(h, w2, b2, w, base)     -> the same value for passes that
+                                            record nothing: second layer and
+                                            combine in one kernel, cg never
+                                            reaches memory.  OPTIONAL (HipOps,
+                                            d = 64), not differentiable
 
   RAW primitives (prefix r_): NON-differentiable single kernels used by
   the hand-sequenced conv backward (distmlip_amd.conv._AtomConvFn),
@@ -52,6 +57,11 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             OPTIONAL (HipOps, d = 64): conv
                                             falls back to the three calls
                                             where a backend lacks it
+    r_mlp_tail_fwd(h, w2, b2, w, base)   -> (cg, out): the second layer's
+                                            batched GEMM and r_combine_fwd as
+                                            one kernel.  OPTIONAL (HipOps,
+                                            d = 64): conv falls back to the
+                                            two calls where a backend lacks it
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

@@ -117,6 +117,25 @@ int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
                               float* dw, int64_t E, int64_t d,
                               uint64_t stream);
 
+/* Fused forward tail of one gated MLP: the second layer over h [E,2d] and
+ * the combine, in one kernel:
+ *   c = h[:, :d] @ w2c + b2c        g = h[:, d:] @ w2g + b2g
+ *   out = (base?base:0) + silu(c) * sigmoid(g) * (w?w:1)
+ * One kernel in place of the batched GEMM + dm_gated_combine_fwd_f32.
+ * w2c, w2g are [d,d] row-major, input x output; b2c, b2g are [d].  c_out and
+ * g_out are both NULL (c and g never reach memory: passes that record
+ * nothing) or both given (any two [E,d] arrays, e.g. the halves of the
+ * packed [2,E,d] buffer dm_gated_mlp_tail_bwd_f32 reads); out is the same
+ * bit for bit either way.  w and base may be NULL.
+ * Compiled for d = 64: any other d, or exactly one of c_out/g_out, returns
+ * an error and launches nothing.  E <= 0 returns 0 without a launch. */
+int dm_gated_mlp_tail_fwd_f32(const float* h, const float* w2c,
+                              const float* w2g, const float* b2c,
+                              const float* b2g, const float* w,
+                              const float* base, float* c_out, float* g_out,
+                              float* out, int64_t E, int64_t d,
+                              uint64_t stream);
+
 /* Fused edge geometry + radial basis (replaces the torch chain for
  * chgnet.py:96-124): per local edge e,
  *   bv[e]  = pos[dst[e]] + offshift[e] - pos[src[e]]
