@@ -19,6 +19,11 @@ and the cross-conv chains.  Default is therefore OFF (DM_FUSED_CONV=1
 opts in); the Function stays as tested infrastructure for the round-2
 whole-graph reverse pass, and the SPMD gloo fp64 exactness tests pin it
 against the oracle (both backends implement the raw primitives).
+
+Checkpointed steps (si1m) take _AtomBlockFn instead: the same atom_fwd /
+atom_bwd inside a node that recomputes itself, with the fused first layer,
+its reverse kernel (gradient sums in the epilogue) and the indexed reverse
+tail; 1205-1210 -> 1096-1102 ms/step at si1m (profiles/first_bwd_*).
 """
 from __future__ import annotations
 
@@ -79,59 +84,137 @@ def _mlp_tail_act(ops, h, w2, b2, w, base, d):
 
 
 def _unpack_edge(packs, d):
-    wcg, bcg, w2, b2 = packs
+    wcg, bcg, w2, b2 = packs[:4]
     return wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:], bcg, w2, b2
 
 
-def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d):
+def _fusedT(packs):
+    """The [d,2d] fusedT pack of a 5-element pack, None for a 4-pack."""
+    return packs[4] if len(packs) > 4 else None
+
+
+def _fused_first(ops, packs, d):
+    """fusedT when the first layer can run as r_edge_mlp3 (5-pack, d = 64,
+    a backend that has it), else None.  DM_NO_FUSED_MLP=1 forces None."""
+    if (d == 64 and hasattr(ops, "r_edge_mlp3")
+            and os.environ.get("DM_NO_FUSED_MLP", "0") != "1"):
+        return _fusedT(packs)
+    return None
+
+
+def _fused_first_bwd(ops, packs, d):
+    """fusedT when the first layer's reverse can run as r_edge_mlp_bwd,
+    else None.  DM_NO_FUSED_MLP1_BWD=1 forces None (addmm, r_gather_dst)."""
+    if (d == 64 and hasattr(ops, "r_edge_mlp_bwd")
+            and os.environ.get("DM_NO_FUSED_MLP1_BWD", "0") != "1"):
+        return _fusedT(packs)
+    return None
+
+
+def _first_fwd(ops, pd, v, e, packs, d):
+    """(z, h) of one MLP's first layer over cat(v[src], v[dst], e)."""
+    ws, wd, we, bcg, _, _ = _unpack_edge(packs, d)
+    ft = _fused_first(ops, packs, d)
+    if ft is not None:
+        return ops.r_edge_mlp3(e, ft, bcg, v @ ws.t(), v @ wd.t(), pd)
+    return ops.r_gather_add3(v @ ws.t(), v @ wd.t(),
+                             torch.addmm(bcg, e, we.t()), pd)
+
+
+def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d,
+             saves_only=False):
     """One atom-conv block forward (chgnet.py:300-313 semantics).
-    Returns (v2, e2, saved) with saved = (z1, cg1, z2, cg2)."""
-    ws1, wd1, we1, bcg1, w21, b21 = _unpack_edge(packs_edge, d)
-    ws2, wd2, we2, bcg2, w22, b22 = _unpack_edge(packs_node, d)
-    z1, h1 = ops.r_gather_add3(v @ ws1.t(), v @ wd1.t(),
-                               torch.addmm(bcg1, e, we1.t()), pd)
+    Returns (v2, e2, saved) with saved = (z1, cg1, z2, cg2).  Packs are
+    (wcg, bcg, w2, b2[, fusedT]); with fusedT and a backend that has
+    r_edge_mlp3 the first layers run as the fused kernel.  saves_only=True
+    (a recomputation) returns (None, None, saved): e2 is freed before the
+    node MLP's tail, where a checkpointed step has its memory peak, and
+    the segment sum is skipped."""
+    _, _, _, _, w21, b21 = _unpack_edge(packs_edge, d)
+    _, _, _, _, w22, b22 = _unpack_edge(packs_node, d)
+    z1, h1 = _first_fwd(ops, pd, v, e, packs_edge, d)
     cg1, e2 = _mlp_tail_fwd(ops, h1, w21, b21, wbb, e, d)
-    z2, h2 = ops.r_gather_add3(v @ ws2.t(), v @ wd2.t(),
-                               torch.addmm(bcg2, e2, we2.t()), pd)
+    del h1
+    z2, h2 = _first_fwd(ops, pd, v, e2, packs_node, d)
+    if saves_only:
+        e2 = None
     cg2, msg = _mlp_tail_fwd(ops, h2, w22, b22, wab, None, d)
-    v2 = ops.r_seg_dst(msg, pd, base=v)
+    del h2
+    v2 = ops.r_seg_dst(msg, pd, base=v) if not saves_only else None
     return v2, e2, (z1, cg1, z2, cg2)
 
 
 def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
-             go_v2, go_e2, acc_wbb=None, acc_wab=None):
+             go_v2, go_e2, acc_wbb=None, acc_wab=None, need_gv=True):
     """Hand-sequenced reverse of atom_fwd.  Returns (gv, ge, dwbb, dwab);
     with acc_wbb/acc_wab buffers the shared-weight grads are ACCUMULATED
     in place (add_) and None returned for them — the cross-block
     accumulation autograd would do with separate elementwise add
-    passes."""
+    passes.
+
+    With 5-packs and a backend that has r_edge_mlp_bwd, the two per-edge
+    reverse GEMMs and the sums they feed are one kernel each, and the
+    node MLP's tail reads go_v2 by pd.dst instead of a gathered copy.
+    saved may be a list: it is emptied, so each save is freed as soon as
+    it is consumed.  need_gv=False skips the four segment sums and GEMMs
+    of the v gradient (gv is None) when v takes no gradient."""
     z1, cg1, z2, cg2 = saved
+    if isinstance(saved, list):
+        saved.clear()
     ws1, wd1, we1, _, w21, _ = _unpack_edge(packs_edge, d)
     ws2, wd2, we2, _, w22, _ = _unpack_edge(packs_node, d)
+    ft1 = _fused_first_bwd(ops, packs_edge, d)
+    ft2 = _fused_first_bwd(ops, packs_node, d)
     go_v2 = go_v2.contiguous() if go_v2 is not None else None
     go_e2 = go_e2.contiguous() if go_e2 is not None else None
 
     # node MLP reverse (v2 = v + seg_dst(msg))
     if go_v2 is not None:
-        dmsg = ops.r_gather_dst(go_v2, pd)
-        dz2, dwab = _mlp_tail_bwd(ops, dmsg, cg2, wab, z2, w22, d)
-        # e2 grad: external + the node MLP's per-edge GEMM, fused
-        ge2 = (torch.addmm(go_e2, dz2, we2) if go_e2 is not None
-               else dz2 @ we2)
+        if (ft2 is not None and getattr(ops, "tail_bwd_indexed", False)
+                and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1"):
+            dz2, dwab = ops.r_mlp_tail_bwd(go_v2, cg2, wab, z2, w22,
+                                           pd.dst)     # go_idx
+        else:
+            dmsg = ops.r_gather_dst(go_v2, pd)
+            dz2, dwab = _mlp_tail_bwd(ops, dmsg, cg2, wab, z2, w22, d)
+            del dmsg
+        del z2, cg2
+        # e2 grad: external + the node MLP's per-edge GEMM, fused.  The
+        # result is a fresh buffer, never go_e2 itself
+        if ft2 is not None:
+            ge2 = ops.r_edge_mlp_bwd(dz2, ft2, go_e2)
+        else:
+            ge2 = (torch.addmm(go_e2, dz2, we2) if go_e2 is not None
+                   else dz2 @ we2)
+        owns_ge2 = True
     else:
+        del z2, cg2
         dz2, dwab = None, None
         ge2 = go_e2
+        owns_ge2 = False
 
     # edge MLP reverse (e2 = e + combine(cg1, wbb))
     dz1, dwbb = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
-    ge = torch.addmm(ge2, dz1, we1)      # base passthrough + GEMM
-    # v grad: passthrough + all four per-node GEMM backs, fused
-    gv = torch.addmm(go_v2, ops.r_seg_src(dz1, pd), ws1) \
-        if go_v2 is not None else ops.r_seg_src(dz1, pd) @ ws1
-    gv.addmm_(ops.r_seg_dst(dz1, pd), wd1)
-    if dz2 is not None:
-        gv.addmm_(ops.r_seg_src(dz2, pd), ws2)
-        gv.addmm_(ops.r_seg_dst(dz2, pd), wd2)
+    del z1, cg1
+    # base passthrough + GEMM; in place only over the ge2 made above
+    if ft1 is not None:
+        ge = ops.r_edge_mlp_bwd(dz1, ft1, ge2,
+                                out=ge2 if owns_ge2 else None)
+    else:
+        ge = torch.addmm(ge2, dz1, we1)
+    del ge2
+    if need_gv:
+        # v grad: passthrough + all four per-node GEMM backs, fused
+        gv = torch.addmm(go_v2, ops.r_seg_src(dz1, pd), ws1) \
+            if go_v2 is not None else ops.r_seg_src(dz1, pd) @ ws1
+        gv.addmm_(ops.r_seg_dst(dz1, pd), wd1)
+        del dz1
+        if dz2 is not None:
+            gv.addmm_(ops.r_seg_src(dz2, pd), ws2)
+            gv.addmm_(ops.r_seg_dst(dz2, pd), wd2)
+            del dz2
+    else:
+        gv = None
     if acc_wbb is not None:
         acc_wbb.add_(dwbb)
         dwbb = None
@@ -325,6 +408,90 @@ def _lean_atom(ops, pd, v, e, wbb, wab, pe, pn, d):
     return ops.scatter_edges(msg, pd, base=v), e2
 
 
+def _block_w(bexp, W, edge_mask):
+    """One shared message weight of a block: bexp @ W.t(), masked."""
+    w = bexp @ W.t()
+    return w if edge_mask is None else w * edge_mask
+
+
+class _AtomBlockFn(torch.autograd.Function):
+    """(v, e, bexp) -> (v', e') for one atom-conv block of a checkpointed
+    step: a self-recomputing node in place of torch.utils.checkpoint around
+    the op-by-op block.
+
+    A Function.forward cannot tell a checkpoint's outer pass from its
+    recomputation, so under the generic checkpoint the outer pass writes z
+    and cg of both MLPs only to have them dropped, and the two gradients of
+    e (erow of an MLP, and base / the next block's input) meet in an
+    elementwise add between autograd nodes.  Here the forward is the
+    save-nothing _lean_atom (no z, no cg) and keeps only v, e, bexp; the
+    backward recomputes the block once in keep form (all at once, as the
+    checkpoint did) and runs the hand-sequenced atom_bwd, where those sums
+    are the epilogue of r_edge_mlp_bwd.
+
+    Wbb / Wab are the [d, n_rbf] weights of the bias-free shared message
+    linears and must be frozen, like the packs pe / pn (5-element, from
+    chgnet._packed_weights); edge_mask is the detached [E,1] verlet mask
+    or None.
+    """
+
+    @staticmethod
+    def forward(ctx, v, e, bexp, Wbb, Wab, edge_mask, pd, ops, pe, pn, d):
+        assert not (Wbb.requires_grad or Wab.requires_grad
+                    or pe[0].requires_grad or pn[0].requires_grad)
+        wbb = _block_w(bexp, Wbb, edge_mask)
+        wab = _block_w(bexp, Wab, edge_mask)
+        # grad mode is off here, but v and e still carry requires_grad, by
+        # which the first-layer Function decides whether to store z:
+        # detached, both MLPs take the no-z form
+        v2, e2 = _lean_atom(ops, pd, v.detach(), e.detach(), wbb, wab, pe,
+                            pn, d)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(v, e, bexp)
+        ctx.consts = (Wbb, Wab, edge_mask, pd, ops, pe, pn, d)
+        return v2, e2
+
+    @staticmethod
+    def backward(ctx, go_v2, go_e2):
+        v, e, bexp = ctx.saved_tensors
+        Wbb, Wab, edge_mask, pd, ops, pe, pn, d = ctx.consts
+        with torch.no_grad():
+            wbb = _block_w(bexp, Wbb, edge_mask)
+            wab = _block_w(bexp, Wab, edge_mask)
+            saved = list(atom_fwd(ops, pd, v, e, wbb, wab, pe, pn, d,
+                                  saves_only=True)[2])
+            gv, ge, dwbb, dwab = atom_bwd(
+                ops, pd, saved, pe, pn, d, wbb, wab, go_v2, go_e2,
+                need_gv=ctx.needs_input_grad[0])
+            del wbb, wab
+            dbexp = None
+            if ctx.needs_input_grad[2]:
+                if edge_mask is not None:
+                    dwbb = dwbb * edge_mask
+                    dwab = dwab * edge_mask if dwab is not None else None
+                dbexp = dwbb @ Wbb
+                if dwab is not None:
+                    dbexp.addmm_(dwab, Wab)
+        return (gv, ge, dbexp, None, None, None, None, None, None, None,
+                None)
+
+
+def atom_block_available(ops, pe, d, dtype) -> bool:
+    """Self-recomputing block policy for checkpointed steps: fp32, d = 64,
+    frozen weights, recording mode, a backend with the raw fused first
+    layer and its reverse.  DM_NO_ATOM_BLOCK=1 keeps torch.utils.checkpoint
+    around the op-by-op block; DM_FUSED_CONV=1 and DM_NO_FUSED_MLP=1 keep
+    their own paths."""
+    return (os.environ.get("DM_NO_ATOM_BLOCK", "0") != "1"
+            and os.environ.get("DM_FUSED_CONV", "0") != "1"
+            and os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
+            and d == 64 and dtype == torch.float32
+            and hasattr(ops, "r_edge_mlp3") and hasattr(ops, "r_edge_mlp_bwd")
+            and hasattr(ops, "edge_mlp3_act")
+            and not pe[0].requires_grad
+            and torch.is_grad_enabled())
+
+
 def _lean_bond(ops, pd, n, a, v, w3, pb, d):
     wcg, bcg, w2, b2, fusedT = pb
     w1, wn2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
@@ -355,6 +522,16 @@ def _lean_angle(ops, pd, n, a, v, pa, d):
 
 def _edge_to_bond(pd, n, e):
     return n.index_copy(0, pd.map_ude, e[pd.map_de])
+
+
+def _keep_packs(pe, pn):
+    """The atom packs _WholeGraphFn's keep mode hands to atom_fwd /
+    atom_bwd: with fusedT, so the fused first layer and its reverse kernels
+    run; DM_NO_ATOM_BLOCK=1 restores the 4-packs (rocBLAS first layer), as
+    it restores the checkpointed steps' op-by-op blocks."""
+    if os.environ.get("DM_NO_ATOM_BLOCK", "0") == "1":
+        return pe[:4], pn[:4]
+    return pe, pn
 
 
 class _WholeGraphFn(torch.autograd.Function):
@@ -391,8 +568,8 @@ class _WholeGraphFn(torch.autograd.Function):
             block_inputs.append((v, e, n, a))
             pe, pn = packs["atom"][i]
             if keep:
-                v, e, sv_at = atom_fwd(ops, pd, v, e, wbb, wab, pe[:4],
-                                       pn[:4], d)
+                v, e, sv_at = atom_fwd(ops, pd, v, e, wbb, wab,
+                                       *_keep_packs(pe, pn), d)
             else:
                 v, e = _lean_atom(ops, pd, v, e, wbb, wab, pe, pn, d)
                 sv_at = None
@@ -419,8 +596,8 @@ class _WholeGraphFn(torch.autograd.Function):
         v_mid, e_mid = v, e
         pe, pn = packs["atom"][nb - 1]
         if keep:
-            v2, _, sv_f = atom_fwd(ops, pd, v, e, wbb, wab, pe[:4],
-                                   pn[:4], d)
+            v2, _, sv_f = atom_fwd(ops, pd, v, e, wbb, wab,
+                                   *_keep_packs(pe, pn), d)
         else:
             v2, _ = _lean_atom(ops, pd, v_mid, e_mid, wbb, wab, pe, pn, d)
             sv_f = None
@@ -448,7 +625,8 @@ class _WholeGraphFn(torch.autograd.Function):
             pe, pn = packs["atom"][nb - 1]
             sv_f = ctx.sv_f
             if sv_f is not None:
-                gv, ge, _, _ = atom_bwd(ops, pd, sv_f, pe[:4], pn[:4], d,
+                gv, ge, _, _ = atom_bwd(ops, pd, sv_f,
+                                        *_keep_packs(pe, pn), d,
                                         wbb, wab, go_v2, None,
                                         acc_wbb=gwbb, acc_wab=gwab)
                 ctx.sv_f = None
@@ -526,7 +704,8 @@ class _WholeGraphFn(torch.autograd.Function):
                     del gn_c
 
                 if sv_at is not None:
-                    gv, ge, _, _ = atom_bwd(ops, pd, sv_at, pe[:4], pn[:4],
+                    gv, ge, _, _ = atom_bwd(ops, pd, sv_at,
+                                            *_keep_packs(pe, pn),
                                             d, wbb, wab, gv, ge,
                                             acc_wbb=gwbb, acc_wab=gwab)
                 else:

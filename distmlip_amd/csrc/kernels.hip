@@ -725,6 +725,13 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 //                    no scratch
 //   <false> (no w):  146 VGPR, 0 AGPR, 68 SGPR, 32 KB LDS, 3 waves/SIMD,
 //                    no scratch
+//   the IDX forms (below): 146 VGPR, 74 / 70 SGPR, otherwise the same
+// Indexed form (IDX, dm_gated_mlp_tail_bwd_idx_f32): go is a [N,64] table
+// and row r reads table row idx[r], one int32 index per lane per tile, loaded
+// inside the live predicate.  This is the reverse of a segment sum feeding
+// the tail (go_msg = go_v[dst]) without the [E,64] gather written and read
+// back; with dst sorted, consecutive rows hit the same 256 B table row.
+// Only the go addresses differ, the arithmetic is that of the plain form.
 // Measured at si1m (rocprofv3 kernel trace, 3 steps): at E = 46M rows with
 // w, 24 launches, 22.5 ms average (21.9-23.6); at L = 12M rows 6.5 ms with
 // w (9 launches) and 5.0 ms without (6).  The chain it replaces took, in
@@ -786,13 +793,14 @@ __device__ __forceinline__ void mlp_tail_epilogue(
 }
 
 // A phase of one tile for one lane: dc|dg of the 32 floats it owns of its
-// row (offset off = row * 64 + 4h), dw stored from there.
+// row (offset off = row * 64 + 4h), dw stored from there.  go is read at
+// goff: off itself, or idx[row] * 64 + 4h in the indexed form.
 template <bool HAS_W>
 __device__ __forceinline__ void mlp_tail_a_phase(
         const float* __restrict__ go, const float* __restrict__ cp,
         const float* __restrict__ gp, const float* __restrict__ wp,
-        float* __restrict__ dw, int64_t off, float (&dcv)[32],
-        float (&dgv)[32]) {
+        float* __restrict__ dw, int64_t off, int64_t goff,
+        float (&dcv)[32], float (&dgv)[32]) {
 #pragma unroll
     for (int i0 = 0; i0 < 8; i0 += TAIL_CHUNK) {
         float4 vgo[TAIL_CHUNK], vc[TAIL_CHUNK], vg[TAIL_CHUNK],
@@ -800,7 +808,7 @@ __device__ __forceinline__ void mlp_tail_a_phase(
 #pragma unroll
         for (int j = 0; j < TAIL_CHUNK; ++j) {
             const int64_t o = off + 8 * (i0 + j);
-            vgo[j] = *(const float4*)(go + o);
+            vgo[j] = *(const float4*)(go + goff + 8 * (i0 + j));
             vc[j] = *(const float4*)(cp + o);
             vg[j] = *(const float4*)(gp + o);
             if (HAS_W) vw[j] = *(const float4*)(wp + o);
@@ -837,9 +845,10 @@ __device__ __forceinline__ void mlp_tail_a_phase(
     }
 }
 
-template <bool HAS_W>
+template <bool HAS_W, bool IDX>
 __global__ __launch_bounds__(256, 3)
-void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]
+void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
+                          const int32_t* __restrict__ idx, // [E], IDX only
                           const float* __restrict__ cp,   // [E,64]
                           const float* __restrict__ gp,   // [E,64]
                           const float* __restrict__ wp,   // [E,64], HAS_W
@@ -883,8 +892,11 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]
         // and store nothing and feed zeros to the MFMAs.  (A predicate on
         // each dw store instead splits the phase into 16 basic blocks and
         // the register allocator then spills 47 VGPRs.)
-        if (live)
-            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, dcv, dgv);
+        if (live) {
+            // IDX: row r's go is row idx[r] of a table, one index per lane
+            const int64_t goff = IDX ? (int64_t)idx[r] * 64 + 4 * h : off;
+            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, goff, dcv, dgv);
+        }
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc[4];
 #pragma unroll
@@ -909,6 +921,144 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]
             mlp_tail_epilogue<true>(acc, z, dz, base, E, c, h);
         else
             mlp_tail_epilogue<false>(acc, z, dz, base, E, c, h);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Reverse of the first layer's per-edge GEMM, with the gradient sum folded
+// in (Din = 128 -> Dout = 64):
+//   out[e,:] = (gbase[e,:] +) dz[e,:] @ WT^T
+// WT [64,128] is the fusedT pack k_edge_mlp_64x128 takes, so this is de of
+// z = erow @ WT + ...; gbase is the other gradient of the same e (e feeds an
+// MLP as erow and flows on as base / to the next block), which autograd
+// would add in a pass of its own.  It replaces a rocBLAS GEMM (or addmm) and
+// that add.
+//
+// Skeleton of k_edge_mlp_64x128: one wave owns 32 rows x 64 columns = 2
+// accumulators (v_mfma_f32_32x32x2_f32, starting at 0), 4 waves per block,
+// grid capped by edge_mlp_blocks so WT is staged once per block.
+//  * B operand: LDS float2 [k][col] = (WT[col][k], WT[32+col][k]), 32 KB;
+//    one ds_read_b64 per k-step feeds the two MFMAs of that step.
+//  * A operand without LDS: dz is row-major, so lane (r = lane&31,
+//    h = lane>>5) reads its own row as 16 float4s at floats [8i+4h, 8i+4h+4);
+//    MFMA step 4i+t contracts k = 8i+4h+t.  128 MFMAs per tile.
+//  * Epilogue in the accumulator layout (col = lane&31, row = (reg&3) +
+//    8*(reg>>2) + 4*(lane>>5)): gbase is loaded 8 rows at a time and added
+//    with one rounding per element, gbase + acc.  A lane reads exactly the
+//    elements it then writes, and tiles own disjoint rows, so out may be
+//    gbase itself (neither pointer is __restrict__).
+//  * Tails: loads of rows >= E are clamped to row E-1, stores predicated;
+//    all row offsets are 64-bit.
+// Algorithmic bytes at 46M rows / 6.29 TB/s: 47.1 GB = 7.5 ms with gbase,
+// 35.3 GB = 5.6 ms without.
+// Resources (hipcc -O3, gfx950, kernel-resource-usage remarks):
+//   <true>  (gbase): 112 VGPR, 0 AGPR, 60 SGPR, 32 KB LDS, 4 waves/SIMD, no
+//                    scratch
+//   <false>:         112 VGPR, 0 AGPR, 26 SGPR, 32 KB LDS, 4 waves/SIMD, no
+//                    scratch
+// (the grid cap of 3 blocks per CU holds either way).
+// Measured at si1m (rocprofv3 kernel trace, 3 steps): at E = 46M rows with
+// gbase 21 launches, 8.58 ms (8.39-8.69), without 3 launches of 6.9 ms; at
+// L = 12M rows without gbase 1.9 ms (15 launches).  The parent's trace of the
+// same run: 8.1-8.3 ms for the GEMM alone plus 8 add launches of 0.7-0.9 ms
+// per sum.  Stand-alone on random inputs, 46M rows, median of 5: 9.47 ms with
+// gbase (in place 9.43) against 16.2 for torch.addmm and 15.0 for mm + add;
+// 7.39 against 8.73 for mm.  Indexed reverse tail in the same runs: 20.0 ms
+// in the trace against 22.4 + 3.1 (k_gather_rows_v4), 22.2 against 28.0
+// stand-alone.
+// ---------------------------------------------------------------------------
+template <bool HAS_BASE, bool FULL>
+__device__ __forceinline__ void edge_mlp_bwd_epilogue(
+        const f32x16 (&acc)[2], const float* gbase, float* out, int64_t base,
+        int64_t E, int c, int h) {
+    constexpr int G = 8;
+#pragma unroll
+    for (int rb = 0; rb < 16; rb += G) {
+        float gv[G][2];
+        if (HAS_BASE) {
+#pragma unroll
+            for (int t = 0; t < G; ++t) {
+                const int r = rb + t;
+                const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t row = base + rl;
+                const int64_t lrow = (FULL || row < E) ? row : E - 1;
+                const float* gp = gbase + lrow * 64 + c;
+                gv[t][0] = gp[0];
+                gv[t][1] = gp[32];
+            }
+            __builtin_amdgcn_sched_barrier(0);   // the batch in flight first
+        }
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t row = base + rl;
+            if (FULL || row < E) {
+                float* op = out + row * 64 + c;
+                op[0] = HAS_BASE ? gv[t][0] + acc[0][r] : acc[0][r];
+                op[32] = HAS_BASE ? gv[t][1] + acc[1][r] : acc[1][r];
+            }
+        }
+    }
+}
+
+template <bool HAS_BASE>
+__global__ __launch_bounds__(256, 3)
+void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
+                    const float* __restrict__ WT,    // [64,128] row-major
+                    const float* gbase,              // [E,64], HAS_BASE
+                    float* out,                      // [E,64], may be gbase
+                    int64_t E) {
+    __shared__ float2 wlds[128 * 32];
+    // i = (col, k) with k fastest: coalesced reads of the row-major WT
+    for (int i = threadIdx.x; i < 128 * 32; i += blockDim.x) {
+        const int k = i & 127, col = i >> 7;
+        wlds[k * 32 + col] = make_float2(WT[col * 128 + k],
+                                         WT[(32 + col) * 128 + k]);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+    const int64_t ntiles = (E + 31) >> 5;
+    const int64_t stride = (int64_t)gridDim.x * waves_per_block;
+    for (int64_t tile = blockIdx.x * (int64_t)waves_per_block + wave;
+         tile < ntiles; tile += stride) {
+        const int64_t base = tile << 5;
+        // opaque copy per tile, as in k_edge_mlp_64x128: keeps the
+        // per-register row offsets from being hoisted and spilled
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int c = lane_t & 31, h = lane_t >> 5;
+        const float2* bl = wlds + (4 * h) * 32 + c;
+        const int64_t r = base + c;
+        const int64_t lrow = r < E ? r : E - 1;   // clamp, never read past E
+        const float4* ap = (const float4*)(dz + lrow * 128) + h;
+        float4 a[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = ap[2 * i];
+        __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
+        f32x16 acc[2];
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[cb][q] = 0.0f;
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float2 b = bl[(8 * i + t) * 32];   // k = 8i + 4h + t
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.y, acc[1], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        if (base + 32 <= E)
+            edge_mlp_bwd_epilogue<HAS_BASE, true>(acc, gbase, out, base, E, c, h);
+        else
+            edge_mlp_bwd_epilogue<HAS_BASE, false>(acc, gbase, out, base, E, c, h);
     }
 }
 
@@ -1899,11 +2049,60 @@ int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
     }
     if (E <= 0) return 0;
     if (w)
-        k_gated_mlp_tail_bwd<true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-            go, c, g, w, z, w2c, w2g, dz, dw, E);
+        k_gated_mlp_tail_bwd<true, false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, nullptr, c, g, w, z, w2c, w2g, dz, dw, E);
     else
-        k_gated_mlp_tail_bwd<false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-            go, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
+        k_gated_mlp_tail_bwd<false, false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, nullptr, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp_tail_bwd_idx_f32(const float* go, const int32_t* idx,
+                                  const float* c, const float* g,
+                                  const float* w, const float* z,
+                                  const float* w2c, const float* w2g,
+                                  float* dz, float* dw, int64_t E, int64_t d,
+                                  uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64) {
+        g_err = "gated_mlp_tail_bwd fused kernel is compiled for d=64";
+        return -1;
+    }
+    if ((w == nullptr) != (dw == nullptr)) {
+        g_err = "gated_mlp_tail_bwd: w and dw must be given together";
+        return -1;
+    }
+    if (idx == nullptr) {
+        g_err = "gated_mlp_tail_bwd_idx: idx must be given";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    if (w)
+        k_gated_mlp_tail_bwd<true, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, idx, c, g, w, z, w2c, w2g, dz, dw, E);
+    else
+        k_gated_mlp_tail_bwd<false, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, idx, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_edge_mlp_bwd_f32(const float* dz, const float* WT, const float* gbase,
+                        float* out, int64_t E, int64_t Din, int64_t Dout,
+                        uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (Din != 128 || Dout != 64) {
+        g_err = "edge_mlp_bwd fused kernel is compiled for Din=128, Dout=64";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    if (gbase)
+        k_edge_mlp_bwd<true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            dz, WT, gbase, out, E);
+    else
+        k_edge_mlp_bwd<false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            dz, WT, nullptr, out, E);
     DM_CHECK_LAUNCH();
     return 0;
 }

@@ -62,6 +62,13 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_gated_mlp_tail_bwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                   fp, fp, c_int64, c_int64,
                                                   c_uint64]
+        lib.dm_gated_mlp_tail_bwd_idx_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_bwd_idx_f32.argtypes = [fp, ip, fp, fp, fp, fp,
+                                                      fp, fp, fp, fp, c_int64,
+                                                      c_int64, c_uint64]
+        lib.dm_edge_mlp_bwd_f32.restype = c_int32
+        lib.dm_edge_mlp_bwd_f32.argtypes = [fp, fp, fp, fp, c_int64, c_int64,
+                                            c_int64, c_uint64]
         lib.dm_gated_mlp_tail_fwd_f32.restype = c_int32
         lib.dm_gated_mlp_tail_fwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                   fp, fp, fp, c_int64,
@@ -261,6 +268,41 @@ class _GatherAdd3(torch.autograd.Function):
         return gzs, gzd, dz, None, None, None, None, None
 
 
+def use_fused_mlp1_bwd() -> bool:
+    """First-layer reverse kernel switch: DM_NO_FUSED_MLP1_BWD=1 restores
+    the rocBLAS GEMM / addmm everywhere, for A/B runs in one build."""
+    return os.environ.get("DM_NO_FUSED_MLP1_BWD", "0") != "1"
+
+
+def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None):
+    """out = (gbase +) dz @ wt.t() in ONE kernel: the reverse of the fused
+    first layer's per-edge GEMM, with the other gradient of the same rows
+    added in its epilogue.  dz [E,128], wt [64,128] (the fusedT pack),
+    gbase [E,64] or None.  out may be gbase (in place); only do that with a
+    buffer the caller owns."""
+    _chk_f32(dz, wt, gbase, out)
+    E = dz.shape[0]
+    assert dz.shape[1] == wt.shape[1]
+    assert gbase is None or gbase.shape == (E, wt.shape[0])
+    if out is None:
+        out = torch.empty(E, wt.shape[0], dtype=dz.dtype, device=dz.device)
+    assert out.shape == (E, wt.shape[0])
+    _check(hip_lib().dm_edge_mlp_bwd_f32(
+        _fp(dz), _fp(wt), _fp(gbase) if gbase is not None else None,
+        _fp(out), E, dz.shape[1], wt.shape[0], _stream()),
+        "dm_edge_mlp_bwd_f32")
+    return out
+
+
+def _first_layer_de(dz, wt):
+    """dz @ wt.t(): dm_edge_mlp_bwd_f32 for the [64,128] pack, else (or
+    with DM_NO_FUSED_MLP1_BWD=1) rocBLAS."""
+    if (tuple(wt.shape) == (64, 128) and dz.dtype == torch.float32
+            and use_fused_mlp1_bwd()):
+        return raw_edge_mlp_bwd(dz, wt)
+    return dz @ wt.t()
+
+
 class _EdgeMlp3(torch.autograd.Function):
     """Fused first-layer edge MLP over the atom graph:
     (z, silu(z)) with z = erow @ WT + bias + zs[src] + zd[dst], the per-edge
@@ -296,7 +338,7 @@ class _EdgeMlp3(torch.autograd.Function):
                               z)
         else:
             dz = go_z.contiguous()
-        de = dz @ wt.t()
+        de = _first_layer_de(dz, wt)
         gzs = raw_seg_sum_gather(dz, src_perm, src_row_ptr, ctx.n_nodes)
         gzd = raw_seg_sum(dz, row_ptr, ctx.n_nodes)
         return de, None, None, gzs, gzd, None, None, None, None, None
@@ -337,7 +379,7 @@ class _EdgeMlp4(torch.autograd.Function):
                               z)
         else:
             dz = go_z.contiguous()
-        da = dz @ wt.t()
+        da = _first_layer_de(dz, wt)
         gz1 = raw_seg_sum_gather(dz, pd.line_src_perm, pd.line_src_row_ptr,
                                  ctx.n_bonds)
         gz2 = raw_seg_sum(dz, pd.line_row_ptr, ctx.n_bonds)
@@ -546,18 +588,34 @@ class _GatedCombinePacked(torch.autograd.Function):
         return dcg, dw, (go if ctx.has_base else None)
 
 
-def raw_mlp_tail_bwd(go, cg, w, z, w2):
+def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None):
     """(dz, dw) of one gated MLP's tail in ONE kernel: the reverse of
     out = base + silu(cg[0]) * sigmoid(cg[1]) * w with cg = the second layer
     over silu(z).  go [E,d], cg [2,E,d] packed, w [E,d] or None, z [E,2d],
-    w2 [2,d,d] (input x output per half).  d must be 64."""
+    w2 [2,d,d] (input x output per half).  d must be 64.  With go_idx
+    (int32 [E]) go is a [N,d] table and row r takes go[go_idx[r]]: the
+    result on the materialized go[go_idx], without that gather."""
     _chk_f32(go, cg, w, z, w2)
-    E, d = go.shape
+    d = go.shape[1]
+    E = go.shape[0] if go_idx is None else go_idx.shape[0]
     assert cg.shape == (2, E, d) and z.shape == (E, 2 * d)
     assert w2.shape == (2, d, d) and (w is None or w.shape == (E, d))
     half = E * d
     dz = torch.empty_like(z)
     dw = torch.empty_like(w) if w is not None else None
+    if go_idx is not None:
+        assert go_idx.dtype == torch.int32 and go_idx.is_contiguous() \
+            and go_idx.device == go.device
+        _check(hip_lib().dm_gated_mlp_tail_bwd_idx_f32(
+            _fp(go), _ip(go_idx),
+            ctypes.cast(cg.data_ptr(), POINTER(c_float)),
+            ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
+            _fp(w) if w is not None else None, _fp(z),
+            ctypes.cast(w2.data_ptr(), POINTER(c_float)),
+            ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
+            _fp(dz), _fp(dw) if dw is not None else None, E, d, _stream()),
+            "dm_gated_mlp_tail_bwd_idx_f32")
+        return dz, dw
     _check(hip_lib().dm_gated_mlp_tail_bwd_f32(
         _fp(go), ctypes.cast(cg.data_ptr(), POINTER(c_float)),
         ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
@@ -659,6 +717,7 @@ class HipOps:
     """Product ops backend (see ops_base.OpsBackend)."""
 
     is_reference = False
+    tail_bwd_indexed = True      # r_mlp_tail_bwd takes go_idx
 
     def gather(self, x, idx, csr=None):
         if csr is None:
@@ -781,10 +840,30 @@ class HipOps:
     def r_silu_bwd(self, go_h, z):
         return raw_silu_bwd(go_h.contiguous(), None, z)
 
-    def r_mlp_tail_bwd(self, go, cg, w, z, w2):
+    def r_mlp_tail_bwd(self, go, cg, w, z, w2, go_idx=None):
         """(dz, dw): r_combine_bwd + second-layer reverse + r_silu_bwd in
-        one kernel (d = 64 only)."""
-        return raw_mlp_tail_bwd(go, cg, w, z, w2)
+        one kernel (d = 64 only).  go_idx: go is a node table read by index
+        (r_gather_dst folded in)."""
+        return raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx)
+
+    def r_edge_mlp3(self, erow, wt, bias, zs, zd, pd):
+        """(z, h) of the fused first layer with z stored: r_gather_add3
+        over addmm(bias, erow, wt) without that [E,2d] transient (wt =
+        the [64,128] fusedT pack only)."""
+        _chk_f32(erow, wt, bias, zs, zd)
+        E, dout = erow.shape[0], wt.shape[1]
+        z = torch.empty(E, dout, dtype=erow.dtype, device=erow.device)
+        h = torch.empty_like(z)
+        _check(hip_lib().dm_edge_mlp3_f32(
+            _fp(erow), _fp(wt), _fp(bias), _fp(zs), _fp(zd), _ip(pd.src),
+            _ip(pd.dst), _fp(z), _fp(h), E, wt.shape[0], dout, _stream()),
+            "dm_edge_mlp3_f32")
+        return z, h
+
+    def r_edge_mlp_bwd(self, dz, wt, gbase=None, out=None):
+        """(gbase +) dz @ wt.t() in one kernel (wt = the [64,128] fusedT
+        pack only); out may be gbase when the caller owns it."""
+        return raw_edge_mlp_bwd(dz, wt, gbase, out)
 
     def r_mlp_tail_fwd(self, h, w2, b2, w, base):
         """(cg, out): second layer + r_combine_fwd in one kernel (d = 64

@@ -56,7 +56,23 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             and r_silu_bwd as one kernel.
                                             OPTIONAL (HipOps, d = 64): conv
                                             falls back to the three calls
-                                            where a backend lacks it
+                                            where a backend lacks it.  A
+                                            backend with the class attribute
+                                            tail_bwd_indexed = True also takes
+                                            go_idx=int32 [E]: go is then a
+                                            [N,d] table read as go[go_idx]
+                                            (r_gather_dst folded in)
+    r_edge_mlp3(e, wt, bias, zs, zd, pd) -> (z, silu(z)) with z = e @ wt +
+                                            bias + zs[src] + zd[dst]: the
+                                            per-edge GEMM inside r_gather_add3.
+                                            OPTIONAL (HipOps, wt [64,128]):
+                                            conv falls back to addmm +
+                                            r_gather_add3
+    r_edge_mlp_bwd(dz, wt, gbase, out)   -> (gbase +) dz @ wt.t(), its
+                                            reverse with the gradient sum in
+                                            the epilogue; out may be gbase.
+                                            OPTIONAL (HipOps, wt [64,128]):
+                                            conv falls back to addmm
     r_mlp_tail_fwd(h, w2, b2, w, base)   -> (cg, out): the second layer's
                                             batched GEMM and r_combine_fwd as
                                             one kernel.  OPTIONAL (HipOps,

@@ -32,8 +32,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from distmlip_amd.conv import (_AtomConvFn, _BondConvFn,
-                               conv_fn_available)
+from distmlip_amd.conv import (_AtomBlockFn, _AtomConvFn, _BondConvFn,
+                               atom_block_available, conv_fn_available)
 from distmlip_amd.chgnet import (
     PartitionData,
     _packed_weights,
@@ -513,6 +513,20 @@ class SpmdEngine:
             return v, e
 
         def atom_conv(layer_i, v, e):
+            if ckpt:
+                # checkpointed steps: the block recomputes itself (lean
+                # outer forward, hand-sequenced reverse) where it can
+                blk = core.atom_convs[layer_i % cfg.n_blocks]
+                pe = _packed_weights(blk.edge_mlp)
+                wbb_w = core.bond_bond_weights.weight
+                wab_w = core.atom_bond_weights.weight
+                if (atom_block_available(ops, pe, d, ft)
+                        and not (wbb_w.requires_grad or wab_w.requires_grad)
+                        and (v.requires_grad or e.requires_grad
+                             or bond_expansion.requires_grad)):
+                    return _AtomBlockFn.apply(
+                        v, e, bond_expansion, wbb_w, wab_w, edge_mask, pd,
+                        ops, pe, _packed_weights(blk.node_mlp), d)
             return _ck(atom_conv_body,
                        torch.tensor(layer_i % cfg.n_blocks), v, e,
                        bond_expansion)

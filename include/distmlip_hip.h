@@ -117,6 +117,30 @@ int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
                               float* dw, int64_t E, int64_t d,
                               uint64_t stream);
 
+/* dm_gated_mlp_tail_bwd_f32 with go read by index: go is a [N,d] table and
+ * row r takes table row idx[r] (int32 [E], every entry in [0,N)), i.e. the
+ * plain entry on the materialized go[idx], bit for bit, without that [E,d]
+ * array being written or read.  Same refusals; idx must not be NULL. */
+int dm_gated_mlp_tail_bwd_idx_f32(const float* go, const int32_t* idx,
+                                  const float* c, const float* g,
+                                  const float* w, const float* z,
+                                  const float* w2c, const float* w2g,
+                                  float* dz, float* dw, int64_t E, int64_t d,
+                                  uint64_t stream);
+
+/* Reverse of the fused first layer's per-edge GEMM with the gradient sum
+ * folded in:  out[e,:] = (gbase ? gbase[e,:] : 0) + dz[e,:] @ WT^T
+ * with dz [E,Din], WT [Dout,Din] row-major (the pack dm_edge_mlp3_f32 /
+ * dm_edge_mlp4_f32 take as their [Din',Dout'] WT), gbase and out [E,Dout].
+ * One kernel in place of a GEMM (or addmm) and an elementwise add.  out may
+ * be gbase itself (each element is read before it is written, by the same
+ * lane); it must not overlap dz.  gbase may be NULL.
+ * Compiled for Din = 128, Dout = 64: anything else returns an error and
+ * launches nothing.  E <= 0 returns 0 without a launch. */
+int dm_edge_mlp_bwd_f32(const float* dz, const float* WT, const float* gbase,
+                        float* out, int64_t E, int64_t Din, int64_t Dout,
+                        uint64_t stream);
+
 /* Fused forward tail of one gated MLP: the second layer over h [E,2d] and
  * the combine, in one kernel:
  *   c = h[:, :d] @ w2c + b2c        g = h[:, d:] @ w2g + b2g
