@@ -121,25 +121,58 @@ def _first_fwd(ops, pd, v, e, packs, d):
                              torch.addmm(bcg, e, we.t()), pd)
 
 
+def _fused_full(ops, d, name):
+    """Whether a whole gated MLP can run as the one-kernel primitive `name`
+    (first layer, second layer and combine, no h array): d = 64 and a backend
+    that has it.  DM_NO_FUSED_MLP_FULL=1 restores the first-layer + tail
+    kernel pair; the switches of those two kernels (DM_NO_FUSED_MLP,
+    DM_NO_FUSED_MLP_FWD) turn it off as well."""
+    return (_fused_tail_fwd(ops, d, name)
+            and os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
+            and os.environ.get("DM_NO_FUSED_MLP_FULL", "0") != "1")
+
+
+def _records(*ts):
+    return torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in ts)
+
+
+def _mlp_fwd(ops, pd, v, ebox, packs, w, base, d, want_out=True):
+    """(z, cg, out) of one atom-graph gated MLP in keep form: one kernel
+    where the backend has r_gated_mlp3 (5-pack, d = 64), else the first
+    layer followed by the tail.  ebox is a one-element list holding the
+    MLP's e rows.  want_out=False: out is not needed.  The one-kernel form
+    then neither computes it nor reads w and base; the two-kernel path
+    empties ebox once the first layer has read the rows, so that a caller
+    who dropped its own reference has them freed before the tail."""
+    ws, wd, _, bcg, w2, b2 = _unpack_edge(packs, d)
+    ft = _fusedT(packs) if _fused_full(ops, d, "r_gated_mlp3") else None
+    if ft is not None:
+        return ops.r_gated_mlp3(ebox[0], ft, bcg, v @ ws.t(), v @ wd.t(), pd,
+                                w2, b2, w, base, want_out)
+    z, h = _first_fwd(ops, pd, v, ebox[0], packs, d)
+    if not want_out:
+        del ebox[:]
+    cg, out = _mlp_tail_fwd(ops, h, w2, b2, w, base, d)
+    return z, cg, out if want_out else None
+
+
 def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d,
              saves_only=False):
     """One atom-conv block forward (chgnet.py:300-313 semantics).
     Returns (v2, e2, saved) with saved = (z1, cg1, z2, cg2).  Packs are
     (wcg, bcg, w2, b2[, fusedT]); with fusedT and a backend that has
-    r_edge_mlp3 the first layers run as the fused kernel.  saves_only=True
-    (a recomputation) returns (None, None, saved): e2 is freed before the
-    node MLP's tail, where a checkpointed step has its memory peak, and
-    the segment sum is skipped."""
-    _, _, _, _, w21, b21 = _unpack_edge(packs_edge, d)
-    _, _, _, _, w22, b22 = _unpack_edge(packs_node, d)
-    z1, h1 = _first_fwd(ops, pd, v, e, packs_edge, d)
-    cg1, e2 = _mlp_tail_fwd(ops, h1, w21, b21, wbb, e, d)
-    del h1
-    z2, h2 = _first_fwd(ops, pd, v, e2, packs_node, d)
+    r_gated_mlp3 each MLP is one kernel, with r_edge_mlp3 alone the first
+    layers are.  saves_only=True (a recomputation) returns (None, None,
+    saved): msg is not needed, so the node MLP runs without out (one kernel)
+    or has e2 freed before its tail (two), where a checkpointed step has
+    its memory peak, and the segment sum is skipped."""
+    z1, cg1, e2 = _mlp_fwd(ops, pd, v, [e], packs_edge, wbb, e, d)
+    ebox = [e2]
     if saves_only:
         e2 = None
-    cg2, msg = _mlp_tail_fwd(ops, h2, w22, b22, wab, None, d)
-    del h2
+    z2, cg2, msg = _mlp_fwd(ops, pd, v, ebox, packs_node, wab, None, d,
+                            want_out=not saves_only)
     v2 = ops.r_seg_dst(msg, pd, base=v) if not saves_only else None
     return v2, e2, (z1, cg1, z2, cg2)
 
@@ -496,6 +529,11 @@ def _lean_bond(ops, pd, n, a, v, w3, pb, d):
     wcg, bcg, w2, b2, fusedT = pb
     w1, wn2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
     wl = ops.gather(w3, pd.l_src, csr=pd.line_src_csr)
+    if (_fused_full(ops, d, "gated_mlp4_act")
+            and not _records(n, a, v, wl)):
+        msg = ops.gated_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
+                                 v @ wv.t(), pd, w2, b2, wl, None)
+        return ops.scatter_lines(msg, pd, base=n)
     if d == 64 and hasattr(ops, "edge_mlp4_act"):
         h = ops.edge_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
                               v @ wv.t(), pd)
@@ -510,6 +548,9 @@ def _lean_bond(ops, pd, n, a, v, w3, pb, d):
 def _lean_angle(ops, pd, n, a, v, pa, d):
     wcg, bcg, w2, b2, fusedT = pa
     w1, wn2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
+    if (_fused_full(ops, d, "gated_mlp4_act") and not _records(n, a, v)):
+        return ops.gated_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
+                                  v @ wv.t(), pd, w2, b2, None, a)
     if d == 64 and hasattr(ops, "edge_mlp4_act"):
         h = ops.edge_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
                               v @ wv.t(), pd)

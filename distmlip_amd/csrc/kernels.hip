@@ -1122,6 +1122,72 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
 //    differs from k_gated_combine_fwd's in the last bit.  The stand-alone
 //    numbers above were taken with that version, the si1m ones with this.
 // ---------------------------------------------------------------------------
+// The epilogue in two parts, so that k_gated_mlp_64 can issue the loads of
+// all 16 rows (G = 16) ahead of its last MFMA run: the w / base loads of rows
+// rb .. rb+G-1 of the accumulator layout, and the c|g stores and the combine
+// of those rows.  OUT = false (k_gated_mlp_64's out-less keep form): c|g are
+// stored and the combine is skipped; w, bs and out are not touched.
+template <bool HAS_W, bool HAS_BASE, bool FULL, int G>
+__device__ __forceinline__ void mlp_tail_fwd_loads(
+        float (&wv)[G][2], float (&bv)[G][2], int rb,
+        const float* __restrict__ w, const float* __restrict__ bs,
+        int64_t base, int64_t E, int c, int h) {
+#pragma unroll
+    for (int t = 0; t < G; ++t) {
+        const int r = rb + t;
+        const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t row = base + rl;
+        const int64_t lrow = (FULL || row < E) ? row : E - 1;
+        if (HAS_W) {
+            wv[t][0] = w[lrow * 64 + c];
+            wv[t][1] = w[lrow * 64 + 32 + c];
+        }
+        if (HAS_BASE) {
+            bv[t][0] = bs[lrow * 64 + c];
+            bv[t][1] = bs[lrow * 64 + 32 + c];
+        }
+    }
+}
+
+template <bool KEEP, bool HAS_W, bool HAS_BASE, bool FULL, bool OUT, int G>
+__device__ __forceinline__ void mlp_tail_fwd_rows(
+        const f32x16 (&acc)[4], const float4 bcol,
+        const float (&wv)[G][2], const float (&bv)[G][2], int rb,
+        float* __restrict__ cout, float* __restrict__ gout,
+        float* __restrict__ out, int64_t base, int64_t E, int c, int h) {
+    static_assert(OUT || (KEEP && !HAS_W && !HAS_BASE),
+                  "the out-less form stores c|g and reads neither w nor base");
+#pragma unroll
+    for (int t = 0; t < G; ++t) {
+        const int r = rb + t;
+        const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t row = base + rl;
+        const float cv[2] = {acc[0][r] + bcol.x, acc[1][r] + bcol.y};
+        const float gv[2] = {acc[2][r] + bcol.z, acc[3][r] + bcol.w};
+        if (FULL || row < E) {
+            const int64_t o = row * 64 + c;
+            if (KEEP) {
+                cout[o] = cv[0]; cout[o + 32] = cv[1];
+                gout[o] = gv[0]; gout[o + 32] = gv[1];
+            }
+#pragma unroll
+            for (int q = 0; OUT && q < 2; ++q) {
+                // k_gated_combine_fwd rounds each product and the
+                // +base separately (its w and base branches keep them
+                // from being contracted to an fma): the same here, so
+                // out equals that kernel's over the same c|g bit for
+                // bit
+#pragma clang fp contract(off)
+                float x = cv[q] * sigf(cv[q]) * sigf(gv[q]);
+                if (HAS_W) x *= wv[t][q];
+                if (HAS_BASE) x += bv[t][q];
+                out[o + 32 * q] = x;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);   // one row at a time
+    }
+}
+
 template <bool KEEP, bool HAS_W, bool HAS_BASE, bool FULL>
 __device__ __forceinline__ void mlp_tail_fwd_epilogue(
         const f32x16 (&acc)[4], const float4 bcol,
@@ -1132,51 +1198,11 @@ __device__ __forceinline__ void mlp_tail_fwd_epilogue(
 #pragma unroll
     for (int rb = 0; rb < 16; rb += G) {
         float wv[G][2], bv[G][2];
-#pragma unroll
-        for (int t = 0; t < G; ++t) {
-            const int r = rb + t;
-            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int64_t row = base + rl;
-            const int64_t lrow = (FULL || row < E) ? row : E - 1;
-            if (HAS_W) {
-                wv[t][0] = w[lrow * 64 + c];
-                wv[t][1] = w[lrow * 64 + 32 + c];
-            }
-            if (HAS_BASE) {
-                bv[t][0] = bs[lrow * 64 + c];
-                bv[t][1] = bs[lrow * 64 + 32 + c];
-            }
-        }
+        mlp_tail_fwd_loads<HAS_W, HAS_BASE, FULL, G>(wv, bv, rb, w, bs, base,
+                                                     E, c, h);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < G; ++t) {
-            const int r = rb + t;
-            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int64_t row = base + rl;
-            const float cv[2] = {acc[0][r] + bcol.x, acc[1][r] + bcol.y};
-            const float gv[2] = {acc[2][r] + bcol.z, acc[3][r] + bcol.w};
-            if (FULL || row < E) {
-                const int64_t o = row * 64 + c;
-                if (KEEP) {
-                    cout[o] = cv[0]; cout[o + 32] = cv[1];
-                    gout[o] = gv[0]; gout[o + 32] = gv[1];
-                }
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    // k_gated_combine_fwd rounds each product and the
-                    // +base separately (its w and base branches keep them
-                    // from being contracted to an fma): the same here, so
-                    // out equals that kernel's over the same c|g bit for
-                    // bit
-#pragma clang fp contract(off)
-                    float x = cv[q] * sigf(cv[q]) * sigf(gv[q]);
-                    if (HAS_W) x *= wv[t][q];
-                    if (HAS_BASE) x += bv[t][q];
-                    out[o + 32 * q] = x;
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);   // one row at a time
-        }
+        mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, FULL, true, G>(
+            acc, bcol, wv, bv, rb, cout, gout, out, base, E, c, h);
     }
 }
 
@@ -1253,6 +1279,318 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
         else
             mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, false>(
                 acc, bcol, w, bs, cout, gout, out, base, E, c, h);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// One whole gated MLP (Din = 64, d = 64) in one kernel: k_edge_mlp_64x128
+// followed by k_gated_mlp_tail_fwd without the h [E,128] array between them.
+//   z   = erow @ WT + bias + g0[i0] + g1[i1] (+ g2[i2])        [E,128]
+//   c|g = silu(z) halves @ w2c|w2g + b2c|b2g                   [E,64] each
+//   out = base + silu(c) * sigmoid(g) * w
+// Forms: no-keep (out only), keep (z, c, g and out), keep without out (z, c,
+// g; w and base are not read: the node MLP of a recomputation).
+//
+// No transposition is needed between the layers: the first product is
+// computed transposed, z^T = WT^T . x^T, by swapping the first two operands
+// of k_edge_mlp_64x128's MFMAs (same LDS image, same per-lane e-row
+// registers).  Register r = 4q+t of column block cb in lane (c, h) then holds
+//   z[base+c][32cb + 8q + 4h + t],
+// which is float t of the float4 slice s = 4(cb&1)+q at floats [8s+4h, +4) of
+// the low (cb 0,1) or high (cb 2,3) half of the lane's OWN row: exactly what
+// k_gated_mlp_tail_fwd loads as alo[s] / ahi[s] and contracts at step 4s+t.
+// After bias, gathers and SiLU the registers are the second layer's A
+// operand as they stand.  Both fma chains keep their k order and products
+// commute, so z, c, g and out equal the two-kernel path's bit for bit; the
+// epilogue adds are in edge_mlp_epilogue's order (acc + bias, += g0 + g1,
+// += g2; bias not folded into the accumulator init, see k_edge_mlp_64x128).
+//
+// Per tile of 32 rows per wave, four MFMA runs of 64: the first layer's core
+// half (z columns 0-63); its gate half, with the core half's epilogue (bias,
+// gathers, SiLU, z stores) in the MFMA gaps; the second layer's c, with the
+// gate half's epilogue in the gaps; the second layer's g; then the parents'
+// tail epilogue (mlp_tail_fwd_rows).  Each accumulator's own chain is in the
+// parents' (i, t) order.  Every lane needs only its own row's indices (no
+// ds_bpermute); gathers and z stores are the lane's own float4 slices, 16 B
+// per lane with 32 distinct rows per instruction (the pattern of the
+// parents' A-operand loads).  Loads are issued a phase or more ahead: a
+// half's gathers before the MFMA run that precedes their use, the next
+// tile's e row and indices as soon as a[] is dead, w and base of all 16
+// accumulator rows before the last MFMA run.
+// Tails: loads of rows >= E are clamped to row E-1, stores predicated; all
+// row offsets are 64-bit.
+// LDS: both weight images, 64 KB + 512 B of bias per block: two blocks of
+// 256 threads per CU, 2 waves/SIMD, grid capped at 512 blocks.
+// Resources (hipcc -O3, gfx950, kernel-resource-usage remarks), all 18
+// variants: NGATHER 2 220-250 VGPR, NGATHER 3 249-255; 0 AGPR, 44-82 SGPR,
+// 66048 B LDS, 2 waves/SIMD, no scratch.  The three-gather variants sit 1-7
+// registers under the 256 of two waves per SIMD: check these remarks after
+// any change here or in the compiler, a spill would not show otherwise.
+// 384-thread blocks (3 waves/SIMD) would need <= 168 VGPR, i.e. none of the
+// look-ahead; not built.
+// Stand-alone at 46M rows (tests/perf_gated_mlp_fused.py, median of 5, ms;
+// the pair = k_edge_mlp_64x128 + k_gated_mlp_tail_fwd in the same run):
+//                     NGATHER 2        NGATHER 3
+//   no-keep w+base    21.5 / 24.7      22.8 / 25.9
+//   no-keep w         20.4 / 24.0      22.0 / 25.4
+//   keep w+base       26.1 / 28.7      28.9 / 31.0
+//   keep w            25.4 / 27.8      28.9 / 29.9
+//   keep, no out      20.8 / 27.8      24.3 / 29.9
+// against 9.6 ms of MFMA time at the 157 TF peak and 7.5 / 15.0 / 9.4 ms of
+// bytes at 6.29 TB/s (no-keep w+base / keep w+base / keep no out).  Every
+// form beats its pair by more than both spreads, by 2-3.5 ms where 9-10 had
+// been estimated (7 ms without out, which is work removed): the time is
+// close to MFMA time plus byte time, as in the parents; the two do not
+// overlap here either.
+// Measured at si1m (rocprofv3 kernel trace, 3 steps, E = 46M rows): keep
+// w+base 12 launches of 24.9 ms (24.9-25.0) against 14 + 13.8 for the pair
+// in the parent's trace of the same session; keep without out 12 launches of
+// 19.1 ms (19.1-19.4) against 14 + 12.9.
+// Tried, same stand-alone run, no-keep w+base / keep w+base / keep no out:
+//  * the plain order (epilogue of a half after its MFMA run, nothing in the
+//    gaps), loads issued where needed: 21.8 / 27.1 / 21.1
+//  * that with the look-ahead loads: 21.3 / 27.3 / 21.3
+//  * no s_setprio: 21.8 / 27.8 / 22.0; s_setprio raised in the epilogues
+//    instead of the MFMA runs: 21.9 / 27.9 / 21.0
+//  * no scheduling barrier between the SiLU slices: 21.7 / 27.0 / 20.7
+//  * this version (epilogues in the MFMA gaps): 21.5 / 26.1 / 20.8; the
+//    three-gather keep-no-out form lost 1 ms by it (23.2 -> 24.3)
+// ---------------------------------------------------------------------------
+constexpr int GATED_MLP_MAX_BLOCKS = 512;   // 256 CUs x 2 resident blocks
+
+inline int gated_mlp_blocks(int64_t rows) {
+    const int64_t tiles = (rows + 31) / 32;         // one 32-row tile per wave
+    const int64_t b = (tiles + BLOCK / 64 - 1) / (BLOCK / 64);
+    return (int)(b < 1 ? 1 : (b > GATED_MLP_MAX_BLOCKS ? GATED_MLP_MAX_BLOCKS : b));
+}
+
+// The lane's own slices of one half (HALF 0: z columns 0-63, 1: 64-127) of
+// its gathered rows; p* point at float 4h of the rows.
+template <int NGATHER, int HALF>
+__device__ __forceinline__ void gated_mlp_gather(
+        float4 (&gv)[NGATHER][8], const float4* __restrict__ p0,
+        const float4* __restrict__ p1, const float4* __restrict__ p2) {
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        gv[0][s] = p0[16 * HALF + 2 * s];
+        gv[1][s] = p1[16 * HALF + 2 * s];
+        if (NGATHER == 3) gv[NGATHER - 1][s] = p2[16 * HALF + 2 * s];
+    }
+}
+
+// First-layer epilogue of slice s of one half, in the transposed accumulator
+// layout: z = acc + bias + gathered slices, hs[s] = silu(z); z stored with
+// KEEP.
+template <int NGATHER, bool KEEP, int HALF>
+__device__ __forceinline__ void gated_mlp_slice_epilogue(
+        const f32x16 (&za)[2], const float4 (&gv)[NGATHER][8],
+        const float4* __restrict__ bias4,   // LDS, at float4 h
+        float4* __restrict__ zrow,          // z_out row, at float4 h
+        bool store, float4 (&hs)[8], int s) {
+    const float4 b = bias4[16 * HALF + 2 * s];
+    const int cb = s >> 2, r0 = 4 * (s & 3);
+    float z[4] = {za[cb][r0 + 0] + b.x, za[cb][r0 + 1] + b.y,
+                  za[cb][r0 + 2] + b.z, za[cb][r0 + 3] + b.w};
+    const float v0[4] = {gv[0][s].x, gv[0][s].y, gv[0][s].z, gv[0][s].w};
+    const float v1[4] = {gv[1][s].x, gv[1][s].y, gv[1][s].z, gv[1][s].w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) z[t] += v0[t] + v1[t];
+    if (NGATHER == 3) {
+        const float4 v2 = gv[NGATHER - 1][s];
+        z[0] += v2.x; z[1] += v2.y; z[2] += v2.z; z[3] += v2.w;
+    }
+    if (KEEP && store)
+        zrow[16 * HALF + 2 * s] = make_float4(z[0], z[1], z[2], z[3]);
+    hs[s] = make_float4(siluf(z[0]), siluf(z[1]), siluf(z[2]), siluf(z[3]));
+}
+
+// One slice's epilogue shares a scheduling region with 8 MFMAs of the run
+// beside it: a v_mfma_f32_32x32x2_f32 holds the matrix pipe for 64 cycles
+// and the wave's own vector instructions issue in that gap, about 14 of
+// them; two waves per SIMD alone did not overlap the two (header comment).
+__device__ __forceinline__ void gated_mlp_interleave() {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, 14, 0);  // 14 VALU
+        __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);   // 1 transcendental
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int NGATHER, bool KEEP, bool OUT, bool HAS_W, bool HAS_BASE>
+__global__ __launch_bounds__(256, 2)
+void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
+                    const float* __restrict__ WT,    // [64,128] row-major
+                    const float* __restrict__ bias,  // [128]
+                    const float* __restrict__ g0,    // [*,128] rows
+                    const float* __restrict__ g1,
+                    const float* __restrict__ g2,    // NGATHER==3 only
+                    const int32_t* __restrict__ i0,
+                    const int32_t* __restrict__ i1,
+                    const int32_t* __restrict__ i2,
+                    const float* __restrict__ w2c,   // [64,64] in x out
+                    const float* __restrict__ w2g,
+                    const float* __restrict__ b2c,   // [64]
+                    const float* __restrict__ b2g,
+                    const float* __restrict__ w,     // [E,64], HAS_W
+                    const float* __restrict__ bs,    // [E,64], HAS_BASE
+                    float* __restrict__ zout,        // [E,128], KEEP
+                    float* __restrict__ cout,        // [E,64], KEEP
+                    float* __restrict__ gout,        // [E,64], KEEP
+                    float* __restrict__ out,         // [E,64], OUT
+                    int64_t E) {
+    // the two parents' LDS images, unchanged
+    __shared__ float4 wl1[64 * 32];
+    __shared__ float4 wl2[64 * 32];
+    __shared__ float4 bias4[32];
+    for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
+        const int k = i >> 5, col = i & 31;
+        const float* p = WT + k * 128 + col;
+        wl1[i] = make_float4(p[0], p[32], p[64], p[96]);
+        wl2[i] = make_float4(w2c[k * 64 + col], w2c[k * 64 + 32 + col],
+                             w2g[k * 64 + col], w2g[k * 64 + 32 + col]);
+    }
+    if (threadIdx.x < 32) {
+        const float* p = bias + 4 * threadIdx.x;
+        bias4[threadIdx.x] = make_float4(p[0], p[1], p[2], p[3]);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int c0 = lane & 31;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+    const float4 bcol = make_float4(b2c[c0], b2c[32 + c0], b2g[c0],
+                                    b2g[32 + c0]);
+    const int64_t ntiles = (E + 31) >> 5;
+    const int64_t stride = (int64_t)gridDim.x * waves_per_block;
+    int64_t tile = blockIdx.x * (int64_t)waves_per_block + wave;
+    if (tile >= ntiles) return;
+    // lane (c, h): its own row's A fragment (floats [8i+4h, +4)) and indices.
+    // Loaded one tile ahead: the loads of tile t+1 are issued as soon as
+    // tile t's last first-layer MFMA has read a[], and are in flight during
+    // the rest of tile t.
+    float4 a[8];
+    int32_t n0, n1, n2 = 0;
+    auto load_tile = [&](int64_t t, int c, int h) {
+        const int64_t r = (t << 5) + c;
+        const int64_t lrow = r < E ? r : E - 1;   // clamp, never read past E
+        // indices first: the gathers wait for them alone
+        n0 = i0[lrow];
+        n1 = i1[lrow];
+        if (NGATHER == 3) n2 = i2[lrow];
+        const float4* ap = (const float4*)(erow + lrow * 64) + h;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] = ap[2 * i];
+    };
+    load_tile(tile, lane & 31, lane >> 5);
+    for (;;) {
+        const int64_t base = tile << 5;
+        // opaque copy per tile, as in the parents: keeps per-register
+        // offsets from being hoisted out of the loop and spilled
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int c = lane_t & 31, h = lane_t >> 5;
+        const float4* bl1 = wl1 + (4 * h) * 32 + c;
+        const float4* bl2 = wl2 + (4 * h) * 32 + c;
+        const int64_t r = base + c;
+        const float4* p0 = (const float4*)(g0 + (int64_t)n0 * 128) + h;
+        const float4* p1 = (const float4*)(g1 + (int64_t)n1 * 128) + h;
+        const float4* p2 = NGATHER == 3
+            ? (const float4*)(g2 + (int64_t)n2 * 128) + h : nullptr;
+        float4* zrow = KEEP ? (float4*)(zout + r * 128) + h : nullptr;
+        const bool live = r < E;
+        float4 gv[NGATHER][8];
+        gated_mlp_gather<NGATHER, 0>(gv, p0, p1, p2);
+        __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
+
+        f32x16 z0[2], z1[2], acc[4];
+        float4 h0s[8], h1s[8];
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                z0[cb][q] = 0.0f; z1[cb][q] = 0.0f;
+                acc[cb][q] = 0.0f; acc[2 + cb][q] = 0.0f;
+            }
+        // a wave inside its MFMA runs outranks waves in their memory phases
+        __builtin_amdgcn_s_setprio(3);
+        // ---- first layer, core half (z columns 0-63) --------------------
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl1[(8 * i + t) * 32];   // k = 8i + 4h + t
+                z0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, av[t], z0[0], 0, 0, 0);
+                z0[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, av[t], z0[1], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- first layer, gate half (z columns 64-127), with the core
+        //      half's epilogue in its MFMA gaps ---------------------------
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl1[(8 * i + t) * 32];
+                z1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, av[t], z1[0], 0, 0, 0);
+                z1[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, av[t], z1[1], 0, 0, 0);
+            }
+            gated_mlp_slice_epilogue<NGATHER, KEEP, 0>(z0, gv, bias4 + h, zrow,
+                                                      live, h0s, i);
+            gated_mlp_interleave();
+        }
+        // the gate half's gathers, then a[] and the indices are dead: the
+        // next tile's (the last tile reloads its own, clamped as ever)
+        gated_mlp_gather<NGATHER, 1>(gv, p0, p1, p2);
+        const int64_t next = tile + stride;
+        const bool more = next < ntiles;
+        load_tile(more ? next : tile, c, h);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- second layer, c, with the gate half's epilogue in its gaps --
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float lo[4] = {h0s[i].x, h0s[i].y, h0s[i].z, h0s[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl2[(8 * i + t) * 32];   // k = 8i + 4h + t
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(lo[t], b.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(lo[t], b.y, acc[1], 0, 0, 0);
+            }
+            gated_mlp_slice_epilogue<NGATHER, KEEP, 1>(z1, gv, bias4 + h, zrow,
+                                                      live, h1s, i);
+            gated_mlp_interleave();
+        }
+        // w and base of all 16 accumulator rows fly during the last MFMA run
+        float wv[16][2], bv[16][2];
+        // (always the clamping form: a branch to the unclamped one on full
+        // tiles spills, 96-344 B of scratch in six variants)
+        mlp_tail_fwd_loads<HAS_W, HAS_BASE, false, 16>(wv, bv, 0, w, bs, base,
+                                                       E, c, h);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- second layer, g ---------------------------------------------
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float hi[4] = {h1s[i].x, h1s[i].y, h1s[i].z, h1s[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 b = bl2[(8 * i + t) * 32];
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi[t], b.z, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi[t], b.w, acc[3], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (base + 32 <= E)
+            mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, true, OUT, 16>(
+                acc, bcol, wv, bv, 0, cout, gout, out, base, E, c, h);
+        else
+            mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, false, OUT, 16>(
+                acc, bcol, wv, bv, 0, cout, gout, out, base, E, c, h);
+        if (!more) break;
+        tile = next;
     }
 }
 
@@ -1875,6 +2213,69 @@ static void launch_mlp_tail_fwd(const float* h, const float* w2c,
                 h, w2c, w2g, b2c, b2g, w, nullptr, c_out, g_out, out, E);
 }
 
+// dm_gated_mlp3/4_f32: checks and launch, by form
+template <int NGATHER>
+static int gated_mlp_run(const float* erow, const float* WT, const float* bias,
+                         const float* g0, const float* g1, const float* g2,
+                         const int32_t* i0, const int32_t* i1,
+                         const int32_t* i2, const float* w2c, const float* w2g,
+                         const float* b2c, const float* b2g, const float* w,
+                         const float* base, float* z_out, float* c_out,
+                         float* g_out, float* out, int64_t E, int64_t Din,
+                         int64_t d, hipStream_t s) {
+    if (Din != 64 || d != 64) {
+        g_err = "gated_mlp fused kernel is compiled for Din=64, d=64";
+        return -1;
+    }
+    if ((c_out == nullptr) != (g_out == nullptr)) {
+        g_err = "gated_mlp: c_out and g_out must be given together";
+        return -1;
+    }
+    if ((z_out == nullptr) != (c_out == nullptr)) {
+        g_err = "gated_mlp: z_out and c_out/g_out must be given together";
+        return -1;
+    }
+    if (!z_out && !out) {
+        g_err = "gated_mlp: the no-keep form needs out";
+        return -1;
+    }
+    if (!i0 || !i1 || (NGATHER == 3 && !i2)) {
+        g_err = "gated_mlp: NULL index";
+        return -1;
+    }
+    if (!erow || !WT || !bias || !g0 || !g1 || (NGATHER == 3 && !g2) || !w2c ||
+        !w2g || !b2c || !b2g) {
+        g_err = "gated_mlp: NULL input";
+        return -1;
+    }
+    // rows are read and written as float4 slices
+    if ((((uintptr_t)erow | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)g2 |
+          (uintptr_t)z_out) & 15) != 0) {
+        g_err = "gated_mlp: erow, the gather tables and z_out must be 16-byte aligned";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    const int grid = gated_mlp_blocks(E);
+#define DM_GMLP_LAUNCH(KEEP, OUT, HW, HB)                                    \
+    k_gated_mlp_64<NGATHER, KEEP, OUT, HW, HB><<<grid, BLOCK, 0, s>>>(       \
+        erow, WT, bias, g0, g1, g2, i0, i1, i2, w2c, w2g, b2c, b2g, w, base, \
+        z_out, c_out, g_out, out, E)
+#define DM_GMLP_WB(KEEP)                                                     \
+    do {                                                                     \
+        if (w && base) DM_GMLP_LAUNCH(KEEP, true, true, true);               \
+        else if (w) DM_GMLP_LAUNCH(KEEP, true, true, false);                 \
+        else if (base) DM_GMLP_LAUNCH(KEEP, true, false, true);              \
+        else DM_GMLP_LAUNCH(KEEP, true, false, false);                       \
+    } while (0)
+    if (!z_out) DM_GMLP_WB(false);
+    else if (out) DM_GMLP_WB(true);
+    else DM_GMLP_LAUNCH(true, false, false, false);   // w, base not read
+#undef DM_GMLP_WB
+#undef DM_GMLP_LAUNCH
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
 // The library's other translation units (tensornet.hip) report through the
 // same per-thread message dm_hip_last_error() returns.  Not exported.
 __attribute__((visibility("hidden")))
@@ -2137,6 +2538,31 @@ int dm_gated_mlp_tail_fwd_f32(const float* h, const float* w2c,
     }
     DM_CHECK_LAUNCH();
     return 0;
+}
+
+int dm_gated_mlp3_f32(const float* erow, const float* WT, const float* bias,
+                      const float* zs, const float* zd, const int32_t* src,
+                      const int32_t* dst, const float* w2c, const float* w2g,
+                      const float* b2c, const float* b2g, const float* w,
+                      const float* base, float* z_out, float* c_out,
+                      float* g_out, float* out, int64_t E, int64_t Din,
+                      int64_t d, uint64_t stream) {
+    return gated_mlp_run<2>(erow, WT, bias, zs, zd, nullptr, src, dst, nullptr,
+                            w2c, w2g, b2c, b2g, w, base, z_out, c_out, g_out,
+                            out, E, Din, d, (hipStream_t)stream);
+}
+
+int dm_gated_mlp4_f32(const float* arow, const float* WT, const float* bias,
+                      const float* z1, const float* z2, const float* zv,
+                      const int32_t* lsrc, const int32_t* ldst,
+                      const int32_t* center, const float* w2c,
+                      const float* w2g, const float* b2c, const float* b2g,
+                      const float* w, const float* base, float* z_out,
+                      float* c_out, float* g_out, float* out, int64_t L,
+                      int64_t Din, int64_t d, uint64_t stream) {
+    return gated_mlp_run<3>(arow, WT, bias, z1, z2, zv, lsrc, ldst, center,
+                            w2c, w2g, b2c, b2g, w, base, z_out, c_out, g_out,
+                            out, L, Din, d, (hipStream_t)stream);
 }
 
 int dm_edge_geom_rbf_fwd_f32(const float* pos, const int32_t* src,

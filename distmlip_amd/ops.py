@@ -73,6 +73,15 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_gated_mlp_tail_fwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                   fp, fp, fp, c_int64,
                                                   c_int64, c_uint64]
+        lib.dm_gated_mlp3_f32.restype = c_int32
+        lib.dm_gated_mlp3_f32.argtypes = [fp, fp, fp, fp, fp, ip, ip, fp, fp,
+                                          fp, fp, fp, fp, fp, fp, fp, fp,
+                                          c_int64, c_int64, c_int64, c_uint64]
+        lib.dm_gated_mlp4_f32.restype = c_int32
+        lib.dm_gated_mlp4_f32.argtypes = [fp, fp, fp, fp, fp, fp, ip, ip, ip,
+                                          fp, fp, fp, fp, fp, fp, fp, fp, fp,
+                                          fp, c_int64, c_int64, c_int64,
+                                          c_uint64]
         lib.dm_mace_tp_fwd_f32.restype = c_int32
         lib.dm_mace_tp_fwd_f32.argtypes = [fp, fp, fp, fp, ip, fp, c_int32,
                                            fp, fp, fp, fp, c_int64, c_int32,
@@ -664,6 +673,71 @@ def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
     return out, cg
 
 
+def use_fused_mlp_full() -> bool:
+    """Whole-MLP kernel switch: DM_NO_FUSED_MLP_FULL=1 restores the
+    first-layer + tail kernel pair everywhere, for A/B runs in one build."""
+    return os.environ.get("DM_NO_FUSED_MLP_FULL", "0") != "1"
+
+
+def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
+                  want_out=True):
+    """One whole gated MLP in ONE kernel (dm_gated_mlp3/4_f32): the fused
+    first layer over row [E,64] and 2 or 3 gathered tables, the second layer
+    and the combine, without the h [E,128] array between them.  Returns
+    (z, cg, out): z [E,128] and cg [2,E,64] packed with keep, else None; out
+    None with want_out=False (keep only; w and base are then not read).
+    Values are the two-kernel path's bit for bit."""
+    _chk_f32(row, wt, bias, *tables, w2, b2, w, base)
+    E, d = row.shape[0], w2.shape[1]
+    assert wt.shape == (d, 2 * d) and w2.shape == (2, d, d)
+    assert b2.numel() == 2 * d and bias.numel() == 2 * d
+    assert len(tables) == len(idx) and len(tables) in (2, 3)
+    assert all(t.shape[1] == 2 * d for t in tables)
+    assert keep or want_out
+    if not want_out:
+        w = base = None
+    assert w is None or w.shape == (E, d)
+    assert base is None or base.shape == (E, d)
+    half = E * d
+    z = torch.empty(E, 2 * d, dtype=row.dtype, device=row.device) \
+        if keep else None
+    if E == 0:
+        e0 = row.new_empty
+        return z, e0(2, 0, d) if keep else None, e0(0, d) if want_out else None
+    cg = torch.empty(2, E, d, dtype=row.dtype, device=row.device) \
+        if keep else None
+    out = torch.empty(E, d, dtype=row.dtype, device=row.device) \
+        if want_out else None
+
+    def at(t, off=0):
+        return ctypes.cast(t.data_ptr() + off, POINTER(c_float))
+    tail = (at(w2), at(w2, 4 * d * d), at(b2), at(b2, 4 * d),
+            _fp(w) if w is not None else None,
+            _fp(base) if base is not None else None,
+            _fp(z) if keep else None,
+            at(cg) if keep else None, at(cg, 4 * half) if keep else None,
+            _fp(out) if want_out else None, E, wt.shape[0], d, _stream())
+    if len(tables) == 2:
+        _check(hip_lib().dm_gated_mlp3_f32(
+            _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
+            _ip(idx[0]), _ip(idx[1]), *tail), "dm_gated_mlp3_f32")
+    else:
+        _check(hip_lib().dm_gated_mlp4_f32(
+            _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
+            _fp(tables[2]), _ip(idx[0]), _ip(idx[1]), _ip(idx[2]), *tail),
+            "dm_gated_mlp4_f32")
+    return z, cg, out
+
+
+def _no_grad_inputs(*ts):
+    return not (torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in ts))
+
+
+def _cont(t):
+    return t.contiguous() if t is not None else None
+
+
 class _GatedMlpTail(torch.autograd.Function):
     """Everything of a gated MLP after its first layer, as one node:
     out = base + silu(c) * sigmoid(g) * w with cg = baddbmm(b2, h halves,
@@ -870,6 +944,27 @@ class HipOps:
         only)."""
         out, cg = raw_mlp_tail_fwd(h, w2, b2, w, base, True)
         return cg, out
+
+    # whole gated MLP in one kernel (first layer, second layer, combine)
+
+    def gated_mlp4_act(self, arow, wt, bias, z1, z2, zv, pd, w2, b2, w=None,
+                       base=None):
+        """mlp_tail_act(edge_mlp4_act(...), w2, b2, w, base) in one kernel,
+        h never reaching memory; for passes that record nothing."""
+        assert _no_grad_inputs(arow, z1, z2, zv, w, base), \
+            "gated_mlp4_act is the no-grad form"
+        return raw_gated_mlp(arow.contiguous(), wt, bias,
+                             (z1.contiguous(), z2.contiguous(),
+                              zv.contiguous()),
+                             (pd.l_src, pd.l_dst, pd.center), w2, b2,
+                             _cont(w), _cont(base), False)[2]
+
+    def r_gated_mlp3(self, erow, wt, bias, zs, zd, pd, w2, b2, w, base,
+                     want_out=True):
+        """(z, cg, out) of r_edge_mlp3 + r_mlp_tail_fwd in one kernel; out
+        is None with want_out=False, and w and base are then not read."""
+        return raw_gated_mlp(erow, wt, bias, (zs, zd), (pd.src, pd.dst), w2,
+                             b2, w, base, True, want_out)
 
     def r_gather_dst(self, x, pd):
         return raw_gather(x.contiguous(), pd.dst)

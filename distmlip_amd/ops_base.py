@@ -40,6 +40,15 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             combine in one kernel, cg never
                                             reaches memory.  OPTIONAL (HipOps,
                                             d = 64), not differentiable
+    gated_mlp4_act(arow, wt, bias, z1, z2, zv, pd, w2, b2, w, base)
+                                         -> mlp_tail_act over edge_mlp4_act as
+                                            ONE kernel, h never reaching
+                                            memory; same value bit for bit.
+                                            OPTIONAL (HipOps, d = 64), not
+                                            differentiable.  (The two-gather
+                                            no-keep form exists as the C entry
+                                            dm_gated_mlp3_f32 only, see
+                                            DESIGN.md §4)
 
   RAW primitives (prefix r_): NON-differentiable single kernels used by
   the hand-sequenced conv backward (distmlip_amd.conv._AtomConvFn),
@@ -78,6 +87,18 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             one kernel.  OPTIONAL (HipOps,
                                             d = 64): conv falls back to the
                                             two calls where a backend lacks it
+    r_gated_mlp3(e, wt, bias, zs, zd, pd, w2, b2, w, base, want_out=True)
+                                         -> (z, cg, out): r_edge_mlp3 and
+                                            r_mlp_tail_fwd as one kernel, same
+                                            values bit for bit; with
+                                            want_out=False out is None and w,
+                                            base are not read.  OPTIONAL
+                                            (HipOps, d = 64): conv falls back
+                                            to the two calls.  (The keep form
+                                            over three gathers exists as the C
+                                            entry dm_gated_mlp4_f32 only:
+                                            bond_fwd / angle_fwd run their
+                                            first layer through rocBLAS)
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

@@ -160,6 +160,39 @@ int dm_gated_mlp_tail_fwd_f32(const float* h, const float* w2c,
                               float* out, int64_t E, int64_t d,
                               uint64_t stream);
 
+/* One whole gated MLP in one kernel: dm_edge_mlp3_f32 followed by
+ * dm_gated_mlp_tail_fwd_f32 without the h [E,2d] array between them:
+ *   z   = erow @ WT + bias + zs[src] + zd[dst]                  [E,2d]
+ *   c   = silu(z)[:, :d] @ w2c + b2c    g = silu(z)[:, d:] @ w2g + b2g
+ *   out = (base?base:0) + silu(c) * sigmoid(g) * (w?w:1)
+ * with every operand laid out as in those two entries.  z, c, g and out are
+ * theirs bit for bit.  Accepted forms:
+ *   no-keep        z_out, c_out, g_out all NULL, out given
+ *   keep           z_out, c_out, g_out and out given
+ *   keep, no out   z_out, c_out, g_out given, out NULL: w and base are not
+ *                  read
+ * erow, zs, zd and z_out must be 16-byte aligned.  Compiled for Din = 64,
+ * d = 64.  Any other size or form, or a NULL index or input, returns an error
+ * and launches nothing.  E <= 0 returns 0 without a launch. */
+int dm_gated_mlp3_f32(const float* erow, const float* WT, const float* bias,
+                      const float* zs, const float* zd, const int32_t* src,
+                      const int32_t* dst, const float* w2c, const float* w2g,
+                      const float* b2c, const float* b2g, const float* w,
+                      const float* base, float* z_out, float* c_out,
+                      float* g_out, float* out, int64_t E, int64_t Din,
+                      int64_t d, uint64_t stream);
+
+/* The three-gather line-graph form over dm_edge_mlp4_f32's operands:
+ *   z = arow @ WT + bias + z1[lsrc] + z2[ldst] + zv[center]. */
+int dm_gated_mlp4_f32(const float* arow, const float* WT, const float* bias,
+                      const float* z1, const float* z2, const float* zv,
+                      const int32_t* lsrc, const int32_t* ldst,
+                      const int32_t* center, const float* w2c,
+                      const float* w2g, const float* b2c, const float* b2g,
+                      const float* w, const float* base, float* z_out,
+                      float* c_out, float* g_out, float* out, int64_t L,
+                      int64_t Din, int64_t d, uint64_t stream);
+
 /* Fused edge geometry + radial basis (replaces the torch chain for
  * chgnet.py:96-124): per local edge e,
  *   bv[e]  = pos[dst[e]] + offshift[e] - pos[src[e]]

@@ -13,7 +13,7 @@ import sys
 
 PATTERNS = ["Cijk_Alik_Bljk", "CUDAFunctor_add", "k_gather_rows_v4",
             "k_edge_mlp_bwd", "k_gated_mlp_tail_bwd", "k_gated_mlp_tail_fwd",
-            "k_edge_mlp_64x128", "k_seg_sum"]
+            "k_gated_mlp_64", "k_edge_mlp_64x128", "k_seg_sum"]
 
 
 def main(d):
