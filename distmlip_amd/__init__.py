@@ -35,3 +35,9 @@ def set_default_dtype(type_: str = "float", size: int = 32):
         raise ValueError("Invalid dtype size")
     if type_ == "float" and size == 16 and not torch.cuda.is_available():
         raise Exception("torch.float16 requires a GPU device")
+
+
+# native MD / relaxation driver (no ASE needed; distmlip_amd/ase.py is the
+# ASE-backed mirror of the reference's classes of the same names)
+from distmlip_amd.md import (EngineForces, MDState,  # noqa: E402,F401
+                             MolecularDynamics, PotentialForces, Relaxer)

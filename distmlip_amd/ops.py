@@ -144,6 +144,17 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_nl_fill_gen_f64.argtypes = nl_gen + [
             cd, cd, cd, ip, ip, POINTER(ctypes.c_int8),
             POINTER(ctypes.c_uint8), c_int64, c_uint64]
+        # MD integrator kernels (distmlip_amd/md_ops.py)
+        vp = ctypes.c_void_p
+        # frac, vel, force, force_f64, inv_mass, xi | a, b, h, c1, c2 |
+        # host: linv9, pbc3
+        lib.dm_md_kick_drift_f64.restype = c_int32
+        lib.dm_md_kick_drift_f64.argtypes = [dp, dp, vp, c_int32, dp, dp,
+                                             cd, cd, cd, cd, cd, dp, ip,
+                                             c_int64, c_uint64]
+        lib.dm_md_kick_reduce_f64.restype = c_int32
+        lib.dm_md_kick_reduce_f64.argtypes = [dp, vp, c_int32, dp, cd, dp,
+                                              dp, c_int64, c_uint64]
         lib.dm_hip_last_error.restype = c_char_p
         _hip_lib = lib
     return _hip_lib

@@ -367,6 +367,46 @@ int dm_tn_msg_bwd_node_f32(const float* G, const float* f, const int32_t* dst,
                            const int32_t* src_row_ptr, float* dY, int64_t N,
                            int32_t C, uint64_t stream);
 
+/* Integrator kernels of the native MD / relaxation driver
+ * (distmlip_amd/md.py; the reference drives ASE's integrators instead,
+ * implementations/matgl/ase.py:130-490).  State is fp64: wrapped fractional
+ * coordinates frac [N,3], cartesian velocities vel [N,3] (A/fs), inv_mass [N]
+ * (NULL = unit masses, FIRE).  `force` [N,3] is fp32 (the engines' output),
+ * or fp64 when force_f64 != 0.  One thread per atom, no atomics; every
+ * expression is evaluated op by op (no fused multiply-add), in the order of
+ * the fp64 torch composition in distmlip_amd/md_ops.py.  frac/vel/force/
+ * inv_mass/xi/partials/out5 are DEVICE arrays; linv9 (row-major inverse
+ * lattice, frac = cart @ Linv) and pbc3 are small HOST arrays passed on to
+ * the kernel by value.  N == 0 launches nothing (kick_reduce then writes
+ * zeros); N >= 2^31-1 returns nonzero.
+ *
+ *   kick_drift: v = a*v + (b*inv_mass)*F, then the displacement
+ *       xi == NULL:  dr = h*v
+ *       xi != NULL:  d1 = (h/2)*v;  v = c1*v + (c2*sqrt(inv_mass))*xi;
+ *                    dr = d1 + (h/2)*v             (the "AOA" of BAOAB)
+ *     then frac_k += (dr_x*Linv[0][k] + dr_y*Linv[1][k]) + dr_z*Linv[2][k]
+ *     and, on periodic dims, f -= floor(f) with a result >= 1.0 (a tiny
+ *     negative f rounds there) replaced by 0.0: frac stays in [0,1), the
+ *     graph builder's contract.  Open dims are left unwrapped.
+ *     a = 1 is the first half of velocity Verlet, a = lambda Berendsen,
+ *     (a, b, h) = (beta, gamma, s*dt) with NULL masses the FIRE update.
+ *
+ *   kick_reduce: v += (b*inv_mass)*F (b == 0: vel is not written), then
+ *     out5 = { sum m v^2, sum F.v, sum |F|^2, sum |v|^2, max_i |F_i|^2 },
+ *     m = 1/inv_mass.  Each block reduces by a fixed tree (wave shuffles,
+ *     LDS across the four waves) and stores one partial per quantity into
+ *     partials [5, ceil(N/256)] (caller-provided scratch); a second
+ *     single-block launch adds those in index order into out5.  The result
+ *     is bit-identical from run to run. */
+int dm_md_kick_drift_f64(double* frac, double* vel, const void* force,
+                         int32_t force_f64, const double* inv_mass,
+                         const double* xi, double a, double b, double h,
+                         double c1, double c2, const double* linv9,
+                         const int32_t* pbc3, int64_t N, uint64_t stream);
+int dm_md_kick_reduce_f64(double* vel, const void* force, int32_t force_f64,
+                          const double* inv_mass, double b, double* partials,
+                          double* out5, int64_t N, uint64_t stream);
+
 const char* dm_hip_last_error(void);
 
 #ifdef __cplusplus
