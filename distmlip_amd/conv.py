@@ -179,7 +179,9 @@ def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d,
 
 def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
              go_v2, go_e2, acc_wbb=None, acc_wab=None, need_gv=True):
-    """Hand-sequenced reverse of atom_fwd.  Returns (gv, ge, dwbb, dwab);
+    """Hand-sequenced reverse of atom_fwd.  Returns (gv, ge, dwbb, dwab), or
+    with factored wbb / wab (ops.RadialW) (gv, ge, dbexp, None), dbexp being
+    the gradient of their common bexp through both weights;
     with acc_wbb/acc_wab buffers the shared-weight grads are ACCUMULATED
     in place (add_) and None returned for them — the cross-block
     accumulation autograd would do with separate elementwise add
@@ -194,6 +196,8 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     z1, cg1, z2, cg2 = saved
     if isinstance(saved, list):
         saved.clear()
+    factored = _is_factored(wbb)
+    assert not factored or (acc_wbb is None and acc_wab is None)
     ws1, wd1, we1, _, w21, _ = _unpack_edge(packs_edge, d)
     ws2, wd2, we2, _, w22, _ = _unpack_edge(packs_node, d)
     ft1 = _fused_first_bwd(ops, packs_edge, d)
@@ -226,7 +230,12 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
         ge2 = go_e2
         owns_ge2 = False
 
-    # edge MLP reverse (e2 = e + combine(cg1, wbb))
+    # edge MLP reverse (e2 = e + combine(cg1, wbb)).  Factored weights: the
+    # node MLP's launch returned its dbexp in dwab; this launch adds its own
+    # onto it in place, and the sum is returned as dwbb
+    if factored and dwab is not None:
+        wbb = wbb.with_acc(dwab)
+        dwab = None
     dz1, dwbb = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
     del z1, cg1
     # base passthrough + GEMM; in place only over the ge2 made above
@@ -447,6 +456,35 @@ def _block_w(bexp, W, edge_mask):
     return w if edge_mask is None else w * edge_mask
 
 
+def _is_factored(w):
+    return hasattr(w, "with_acc")        # ops.RadialW
+
+
+def _factored_w(ops, bexp, d):
+    """Whether a block hands its two message weights to the MLP tail kernels
+    as factors (ops.RadialW: bexp, W, mask) instead of building the dense
+    [E,d] arrays: a backend that takes them (fp32, d = 64, n_rbf = 9), and the
+    fused tails in use.  DM_NO_FACTORED_W=1 restores the dense weights."""
+    return (getattr(ops, "factored_w", False) and d == 64
+            and bexp.dtype == torch.float32 and bexp.shape[1] == 9
+            and os.environ.get("DM_NO_FACTORED_W", "0") != "1"
+            and os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1"
+            and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1")
+
+
+def _block_weights(ops, bexp, Wbb, Wab, edge_mask, d):
+    """(wbb, wab) of a block: factored where _factored_w allows, else the two
+    dense arrays of _block_w."""
+    if _factored_w(ops, bexp, d):
+        from .ops import RadialW
+        bexp = bexp.detach().contiguous()
+        mask = edge_mask.reshape(-1).contiguous() \
+            if edge_mask is not None else None
+        return (RadialW(bexp, Wbb.contiguous(), mask),
+                RadialW(bexp, Wab.contiguous(), mask))
+    return _block_w(bexp, Wbb, edge_mask), _block_w(bexp, Wab, edge_mask)
+
+
 class _AtomBlockFn(torch.autograd.Function):
     """(v, e, bexp) -> (v', e') for one atom-conv block of a checkpointed
     step: a self-recomputing node in place of torch.utils.checkpoint around
@@ -462,6 +500,11 @@ class _AtomBlockFn(torch.autograd.Function):
     checkpoint did) and runs the hand-sequenced atom_bwd, where those sums
     are the epilogue of r_edge_mlp_bwd.
 
+    Where the backend takes factored weights (_factored_w) the two shared
+    message weights are never built: the tail kernels get bexp, Wbb / Wab and
+    the mask and compute w in place, and the reverse tails return dbexp
+    directly instead of two dense [E,d] gradients folded by two GEMMs.
+
     Wbb / Wab are the [d, n_rbf] weights of the bias-free shared message
     linears and must be frozen, like the packs pe / pn (5-element, from
     chgnet._packed_weights); edge_mask is the detached [E,1] verlet mask
@@ -472,8 +515,7 @@ class _AtomBlockFn(torch.autograd.Function):
     def forward(ctx, v, e, bexp, Wbb, Wab, edge_mask, pd, ops, pe, pn, d):
         assert not (Wbb.requires_grad or Wab.requires_grad
                     or pe[0].requires_grad or pn[0].requires_grad)
-        wbb = _block_w(bexp, Wbb, edge_mask)
-        wab = _block_w(bexp, Wab, edge_mask)
+        wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
         # grad mode is off here, but v and e still carry requires_grad, by
         # which the first-layer Function decides whether to store z:
         # detached, both MLPs take the no-z form
@@ -489,16 +531,19 @@ class _AtomBlockFn(torch.autograd.Function):
         v, e, bexp = ctx.saved_tensors
         Wbb, Wab, edge_mask, pd, ops, pe, pn, d = ctx.consts
         with torch.no_grad():
-            wbb = _block_w(bexp, Wbb, edge_mask)
-            wab = _block_w(bexp, Wab, edge_mask)
+            wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
             saved = list(atom_fwd(ops, pd, v, e, wbb, wab, pe, pn, d,
                                   saves_only=True)[2])
             gv, ge, dwbb, dwab = atom_bwd(
                 ops, pd, saved, pe, pn, d, wbb, wab, go_v2, go_e2,
                 need_gv=ctx.needs_input_grad[0])
+            factored = _is_factored(wbb)
             del wbb, wab
             dbexp = None
-            if ctx.needs_input_grad[2]:
+            if factored:
+                # the two tail launches produced it, mask applied
+                dbexp = dwbb if ctx.needs_input_grad[2] else None
+            elif ctx.needs_input_grad[2]:
                 if edge_mask is not None:
                     dwbb = dwbb * edge_mask
                     dwab = dwab * edge_mask if dwab is not None else None

@@ -726,6 +726,13 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 //   <false> (no w):  146 VGPR, 0 AGPR, 68 SGPR, 32 KB LDS, 3 waves/SIMD,
 //                    no scratch
 //   the IDX forms (below): 146 VGPR, 74 / 70 SGPR, otherwise the same
+//   <2> (factored w, dm_gated_mlp_tail_bwd_fw_f32; bexp, W, mask in, dbexp
+//        out, see radial_w and DM_FW_BWD_WAVES): 242 VGPR, 0 AGPR, 77 SGPR
+//        (IDX 79), 35 KB LDS, 2 waves/SIMD, no scratch; grid capped at
+//        gated_mlp_blocks.  The 9-term product and its reverse are VALU
+//        work (18 fma per column and row beside 2 sigmoids; as MFMAs they
+//        would be a K = 9 product and a 32-step chain on a fifth
+//        accumulator, 64 more registers)
 // Indexed form (IDX, dm_gated_mlp_tail_bwd_idx_f32): go is a [N,64] table
 // and row r reads table row idx[r], one int32 index per lane per tile, loaded
 // inside the live predicate.  This is the reverse of a segment sum feeding
@@ -792,15 +799,67 @@ __device__ __forceinline__ void mlp_tail_epilogue(
     }
 }
 
+// Factored message weight (HAS_W == 2 in the three gated-MLP kernels below):
+// w[r][col] = mask[r] * sum_k bexp[r][k] * W[col][k] with bexp [E,9], W [64,9]
+// row-major and mask [E] (or none: 1), computed where it is used instead of
+// read from a dense [E,64] array.  ONE fp32 order everywhere: b0 * W0, then an
+// fma chain over k = 1..8 ascending, the mask multiplied last.  The forward
+// tail, the one-kernel MLP and the reverse tail all call radial_w, so an outer
+// forward, its recomputation and the reverse see the same w bit for bit.
+// W rows live in LDS padded to 12 floats (three 16-byte reads per row).
+constexpr int N_RBF = 9;
+constexpr int RBF_PAD = 12;
+
+__device__ __forceinline__ float radial_w(const float (&b)[N_RBF],
+                                          const float (&wc)[N_RBF], float m) {
+    float a = b[0] * wc[0];
+#pragma unroll
+    for (int k = 1; k < N_RBF; ++k) a = __builtin_fmaf(b[k], wc[k], a);
+    return a * m;
+}
+
+// 9 floats of a padded LDS row (16-byte aligned); p3 receives float 9..11.
+// The empty asm statements keep each 16-byte read whole: left alone, the
+// compiler narrows the row to the 9 floats in use and reads them as one
+// ds_read_b96 and three ds_read2_b32, each with an address register of its
+// own (308 B of scratch per lane in the reverse kernel).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void radial_row(const float4* __restrict__ p,
+                                           float (&v)[N_RBF], float4& p3) {
+    const f32x4* q = (const f32x4*)p;
+    f32x4 a = q[0], b = q[1], c = q[2];
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c));
+    p3 = make_float4(c.x, c.y, c.z, c.w);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    v[8] = p3.x;
+}
+
+// W [64,9] into the padded LDS image, by the whole block
+__device__ __forceinline__ void radial_stage_W(float* __restrict__ wl9,
+                                               const float* __restrict__ W) {
+    for (int i = threadIdx.x; i < 64 * RBF_PAD; i += blockDim.x) {
+        const int col = i / RBF_PAD, k = i - col * RBF_PAD;
+        wl9[i] = k < N_RBF ? W[col * N_RBF + k] : 0.0f;
+    }
+}
+
 // A phase of one tile for one lane: dc|dg of the 32 floats it owns of its
 // row (offset off = row * 64 + 4h), dw stored from there.  go is read at
 // goff: off itself, or idx[row] * 64 + 4h in the indexed form.
-template <bool HAS_W>
+// HAS_W == 2: w of the lane's 32 columns comes from its bexp row bx (9
+// registers) and mask m, and the W rows of those columns, the same for all
+// lanes of a half-wave, from LDS (wl9 points at row 4h: broadcast reads);
+// instead of the dw store, dbp[k] += dw[col] * W[col][k], columns ascending.
+template <int HAS_W>
 __device__ __forceinline__ void mlp_tail_a_phase(
         const float* __restrict__ go, const float* __restrict__ cp,
         const float* __restrict__ gp, const float* __restrict__ wp,
         float* __restrict__ dw, int64_t off, int64_t goff,
-        float (&dcv)[32], float (&dgv)[32]) {
+        float (&dcv)[32], float (&dgv)[32],
+        const float4* __restrict__ wl9, const float (&bx)[N_RBF], float m,
+        float (&dbp)[N_RBF]) {
 #pragma unroll
     for (int i0 = 0; i0 < 8; i0 += TAIL_CHUNK) {
         float4 vgo[TAIL_CHUNK], vc[TAIL_CHUNK], vg[TAIL_CHUNK],
@@ -811,7 +870,7 @@ __device__ __forceinline__ void mlp_tail_a_phase(
             vgo[j] = *(const float4*)(go + goff + 8 * (i0 + j));
             vc[j] = *(const float4*)(cp + o);
             vg[j] = *(const float4*)(gp + o);
-            if (HAS_W) vw[j] = *(const float4*)(wp + o);
+            if (HAS_W == 1) vw[j] = *(const float4*)(wp + o);
         }
         __builtin_amdgcn_sched_barrier(0);   // the batch in flight first
 #pragma unroll
@@ -820,15 +879,27 @@ __device__ __forceinline__ void mlp_tail_a_phase(
             const float cv4[4] = {vc[j].x, vc[j].y, vc[j].z, vc[j].w};
             const float gv4[4] = {vg[j].x, vg[j].y, vg[j].z, vg[j].w};
             float wv4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-            if (HAS_W) {
+            if (HAS_W == 1) {
                 wv4[0] = vw[j].x; wv4[1] = vw[j].y;
                 wv4[2] = vw[j].z; wv4[3] = vw[j].w;
             }
-            float dwv[4];
+            float dwv[4], sc4[4], sg4[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const float gov = gov4[t], cv = cv4[t], gv = gv4[t];
-                const float sc = sigf(cv), sg = sigf(gv);
+                sc4[t] = sigf(cv4[t]);
+                sg4[t] = sigf(gv4[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                float wc[N_RBF];
+                if (HAS_W == 2) {
+                    float4 pad;                  // col = 8(i0+j) + 4h + t
+                    radial_row(wl9 + (8 * (i0 + j) + t) * (RBF_PAD / 4), wc,
+                               pad);
+                    wv4[t] = radial_w(bx, wc, m);
+                }
+                const float gov = gov4[t], cv = cv4[t];
+                const float sc = sc4[t], sg = sg4[t];
                 const float silu_c = cv * sc;
                 const float wv = wv4[t];
                 dcv[4 * (i0 + j) + t] =
@@ -836,8 +907,13 @@ __device__ __forceinline__ void mlp_tail_a_phase(
                 dgv[4 * (i0 + j) + t] =
                     gov * wv * silu_c * (sg * (1.0f - sg));
                 dwv[t] = gov * silu_c * sg;
+                if (HAS_W == 2) {
+#pragma unroll
+                    for (int k = 0; k < N_RBF; ++k)
+                        dbp[k] = __builtin_fmaf(dwv[t], wc[k], dbp[k]);
+                }
             }
-            if (HAS_W)
+            if (HAS_W == 1)
                 *(float4*)(dw + off + 8 * (i0 + j)) =
                     make_float4(dwv[0], dwv[1], dwv[2], dwv[3]);
             __builtin_amdgcn_sched_barrier(0);   // one slice at a time
@@ -845,20 +921,40 @@ __device__ __forceinline__ void mlp_tail_a_phase(
     }
 }
 
-template <bool HAS_W, bool IDX>
-__global__ __launch_bounds__(256, 3)
+// Waves per SIMD of the factored reverse tail.  Its A phase holds 31 more
+// registers than the dense one (bexp row, mask, dbexp partials, a W row) next
+// to the 64 of dc|dg: within the 168 registers of three waves per SIMD the
+// compiler spills 47 of them (188 B of scratch per lane, with load batches of
+// 1, 2 or 4 slices alike), at two it takes 242 and none.  2 is the build;
+// -DDM_FW_BWD_WAVES=3 builds the spilling form for comparison
+// (tests/perf_factored_w.py, profiles/factored_w_standalone.json).
+#ifndef DM_FW_BWD_WAVES
+#define DM_FW_BWD_WAVES 2
+#endif
+
+template <int HAS_W, bool IDX>
+__global__ __launch_bounds__(256, HAS_W == 2 ? DM_FW_BWD_WAVES : 3)
 void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
                           const int32_t* __restrict__ idx, // [E], IDX only
                           const float* __restrict__ cp,   // [E,64]
                           const float* __restrict__ gp,   // [E,64]
-                          const float* __restrict__ wp,   // [E,64], HAS_W
+                          const float* __restrict__ wp,   // [E,64], HAS_W;
+                                                          // 2: bexp [E,9]
                           const float* __restrict__ z,    // [E,128]
                           const float* __restrict__ w2c,  // [64,64] in x out
                           const float* __restrict__ w2g,
                           float* __restrict__ dz,         // [E,128]
-                          float* __restrict__ dw,         // [E,64], HAS_W
-                          int64_t E) {
+                          float* __restrict__ dw,         // [E,64], HAS_W 1
+                          int64_t E,
+                          // HAS_W == 2 only
+                          const float* __restrict__ fwW,  // [64,9]
+                          const float* __restrict__ fwmask,  // [E] or null
+                          const float* dbexp_in,          // [E,9] or null
+                          float* dbexp) {                 // [E,9], may be
+                                                          // dbexp_in
     __shared__ float4 wlds[64 * 32];
+    __shared__ float4 wl9[HAS_W == 2 ? 64 * RBF_PAD / 4 : 1];
+    if (HAS_W == 2) radial_stage_W((float*)wl9, fwW);
     // i = (col, k) with k fastest: coalesced reads of the row-major blocks
     for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
         const int k = i & 63, col = i >> 6;
@@ -892,10 +988,41 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
         // and store nothing and feed zeros to the MFMAs.  (A predicate on
         // each dw store instead splits the phase into 16 basic blocks and
         // the register allocator then spills 47 VGPRs.)
+        float bx[N_RBF], dbp[N_RBF], msk = 1.0f;
+#pragma unroll
+        for (int k = 0; k < N_RBF; ++k) bx[k] = dbp[k] = 0.0f;
         if (live) {
             // IDX: row r's go is row idx[r] of a table, one index per lane
             const int64_t goff = IDX ? (int64_t)idx[r] * 64 + 4 * h : off;
-            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, goff, dcv, dgv);
+            if (HAS_W == 2) {
+#pragma unroll
+                for (int k = 0; k < N_RBF; ++k) bx[k] = wp[r * N_RBF + k];
+                if (fwmask) msk = fwmask[r];
+            }
+            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, goff, dcv, dgv,
+                                    wl9 + (4 * h) * (RBF_PAD / 4), bx, msk,
+                                    dbp);
+        }
+        if (HAS_W == 2) {
+            // dbexp[r][k] = mask[r] * (h=0 partial + h=1 partial) + dbexp_in:
+            // the lane's columns ascending (above), then the two half-waves
+            // (the sum commutes, both halves hold the same bits), the mask,
+            // then dbexp_in, each rounded on its own.  Lane h = 0 of the row
+            // reads and writes its 9 floats, so dbexp may be dbexp_in.
+#pragma clang fp contract(off)
+            float ds[N_RBF];
+#pragma unroll
+            for (int k = 0; k < N_RBF; ++k)
+                ds[k] = (dbp[k] + __shfl_xor(dbp[k], 32, 64)) * msk;
+            if (live && h == 0) {
+                if (dbexp_in) {
+#pragma unroll
+                    for (int k = 0; k < N_RBF; ++k)
+                        ds[k] += dbexp_in[r * N_RBF + k];
+                }
+#pragma unroll
+                for (int k = 0; k < N_RBF; ++k) dbexp[r * N_RBF + k] = ds[k];
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc[4];
@@ -1097,6 +1224,9 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
 // Resources (hipcc -O3, gfx950, kernel-resource-usage remarks), all eight
 // <KEEP, HAS_W, HAS_BASE> variants: 152 VGPR, 0 AGPR, 31-68 SGPR, 32 KB LDS,
 // 3 waves/SIMD, no scratch.
+// The four factored-w variants <KEEP, 2, HAS_BASE>
+// (dm_gated_mlp_tail_fwd_fw_f32): 162 VGPR, 0 AGPR, 50-86 SGPR, 41 KB LDS
+// (W image 3 KB, bexp regions 6 KB), 3 waves/SIMD, no scratch.
 // Measured at si1m (rocprofv3 kernel trace, 3 steps; every launch there is a
 // KEEP one): at E = 46M rows with w and base, 24 launches, 13.8 ms average
 // (13.65-14.43); with w alone 12.85 ms (12.68-12.98); at L = 12M rows 3.8
@@ -1127,7 +1257,53 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
 // rb .. rb+G-1 of the accumulator layout, and the c|g stores and the combine
 // of those rows.  OUT = false (k_gated_mlp_64's out-less keep form): c|g are
 // stored and the combine is skipped; w, bs and out are not touched.
-template <bool HAS_W, bool HAS_BASE, bool FULL, int G>
+//
+// HAS_W == 2 (factored w, see radial_w): nothing of w is loaded per row.  A
+// wave stages its tile's bexp block, 32 x 9 contiguous floats, and the 32 mask
+// values in an LDS region of its own, rows padded to 12 floats with the mask
+// in float 9 (radial_tile_load issues the 6 loads per lane, radial_tile_store
+// writes them once they have landed; rows >= E get zeros, and are never
+// stored).  The epilogue reads a row as three 16-byte broadcast reads per
+// half-wave and combines it with the lane's two W rows (18 registers, read
+// from the padded LDS image of W once per tile).  LDS operations of one wave
+// execute in order, so the region needs no barrier between a tile's reads and
+// the next tile's writes.
+constexpr int RBF_TILE = 32 * RBF_PAD;      // floats of one wave's region
+
+__device__ __forceinline__ void radial_tile_load(
+        float (&sv)[6], const float* __restrict__ bexp,
+        const float* __restrict__ mask, int64_t base, int64_t E, int lane) {
+    const int64_t o = base * N_RBF, lim = E * N_RBF;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int i = lane + 64 * j;
+        sv[j] = (i < 32 * N_RBF && o + i < lim) ? bexp[o + i] : 0.0f;
+    }
+    const int64_t row = base + (lane & 31);
+    sv[5] = row < E ? (mask ? mask[row] : 1.0f) : 0.0f;
+}
+
+__device__ __forceinline__ void radial_tile_store(
+        float* __restrict__ st, const float (&sv)[6], int lane) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int i = lane + 64 * j;
+        const int row = i / N_RBF;
+        if (i < 32 * N_RBF) st[row * RBF_PAD + (i - row * N_RBF)] = sv[j];
+    }
+    if (lane < 32) st[lane * RBF_PAD + N_RBF] = sv[5];
+    __builtin_amdgcn_wave_barrier();   // no read of the region moves above
+}
+
+// the lane's two W rows (columns c and 32 + c) from the padded LDS image
+__device__ __forceinline__ void radial_lane_W(
+        float (&wc)[2][N_RBF], const float4* __restrict__ wl9, int c) {
+    float4 pad;
+    radial_row(wl9 + c * (RBF_PAD / 4), wc[0], pad);
+    radial_row(wl9 + (32 + c) * (RBF_PAD / 4), wc[1], pad);
+}
+
+template <int HAS_W, bool HAS_BASE, bool FULL, int G>
 __device__ __forceinline__ void mlp_tail_fwd_loads(
         float (&wv)[G][2], float (&bv)[G][2], int rb,
         const float* __restrict__ w, const float* __restrict__ bs,
@@ -1138,7 +1314,7 @@ __device__ __forceinline__ void mlp_tail_fwd_loads(
         const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
         const int64_t row = base + rl;
         const int64_t lrow = (FULL || row < E) ? row : E - 1;
-        if (HAS_W) {
+        if (HAS_W == 1) {
             wv[t][0] = w[lrow * 64 + c];
             wv[t][1] = w[lrow * 64 + 32 + c];
         }
@@ -1149,12 +1325,15 @@ __device__ __forceinline__ void mlp_tail_fwd_loads(
     }
 }
 
-template <bool KEEP, bool HAS_W, bool HAS_BASE, bool FULL, bool OUT, int G>
+// st4 (HAS_W == 2): the wave's staged bexp region at row 4h; wc: the lane's
+// two W rows.
+template <bool KEEP, int HAS_W, bool HAS_BASE, bool FULL, bool OUT, int G>
 __device__ __forceinline__ void mlp_tail_fwd_rows(
         const f32x16 (&acc)[4], const float4 bcol,
         const float (&wv)[G][2], const float (&bv)[G][2], int rb,
         float* __restrict__ cout, float* __restrict__ gout,
-        float* __restrict__ out, int64_t base, int64_t E, int c, int h) {
+        float* __restrict__ out, int64_t base, int64_t E, int c, int h,
+        const float4* __restrict__ st4, const float (&wc)[2][N_RBF]) {
     static_assert(OUT || (KEEP && !HAS_W && !HAS_BASE),
                   "the out-less form stores c|g and reads neither w nor base");
 #pragma unroll
@@ -1164,6 +1343,17 @@ __device__ __forceinline__ void mlp_tail_fwd_rows(
         const int64_t row = base + rl;
         const float cv[2] = {acc[0][r] + bcol.x, acc[1][r] + bcol.y};
         const float gv[2] = {acc[2][r] + bcol.z, acc[3][r] + bcol.w};
+        float wq[2] = {1.0f, 1.0f};
+        if (HAS_W == 1) {
+            wq[0] = wv[t][0]; wq[1] = wv[t][1];
+        }
+        if (HAS_W == 2) {
+            float bx[N_RBF];
+            float4 p3;                           // p3.y: the row's mask
+            radial_row(st4 + ((r & 3) + 8 * (r >> 2)) * (RBF_PAD / 4), bx, p3);
+            wq[0] = radial_w(bx, wc[0], p3.y);
+            wq[1] = radial_w(bx, wc[1], p3.y);
+        }
         if (FULL || row < E) {
             const int64_t o = row * 64 + c;
             if (KEEP) {
@@ -1179,7 +1369,7 @@ __device__ __forceinline__ void mlp_tail_fwd_rows(
                 // bit
 #pragma clang fp contract(off)
                 float x = cv[q] * sigf(cv[q]) * sigf(gv[q]);
-                if (HAS_W) x *= wv[t][q];
+                if (HAS_W) x *= wq[q];
                 if (HAS_BASE) x += bv[t][q];
                 out[o + 32 * q] = x;
             }
@@ -1188,13 +1378,16 @@ __device__ __forceinline__ void mlp_tail_fwd_rows(
     }
 }
 
-template <bool KEEP, bool HAS_W, bool HAS_BASE, bool FULL>
+template <bool KEEP, int HAS_W, bool HAS_BASE, bool FULL>
 __device__ __forceinline__ void mlp_tail_fwd_epilogue(
         const f32x16 (&acc)[4], const float4 bcol,
         const float* __restrict__ w, const float* __restrict__ bs,
         float* __restrict__ cout, float* __restrict__ gout,
-        float* __restrict__ out, int64_t base, int64_t E, int c, int h) {
+        float* __restrict__ out, int64_t base, int64_t E, int c, int h,
+        const float4* __restrict__ wl9, const float4* __restrict__ st4) {
     constexpr int G = 8;
+    float wc[2][N_RBF];
+    if (HAS_W == 2) radial_lane_W(wc, wl9, c);
 #pragma unroll
     for (int rb = 0; rb < 16; rb += G) {
         float wv[G][2], bv[G][2];
@@ -1202,24 +1395,31 @@ __device__ __forceinline__ void mlp_tail_fwd_epilogue(
                                                      E, c, h);
         __builtin_amdgcn_sched_barrier(0);
         mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, FULL, true, G>(
-            acc, bcol, wv, bv, rb, cout, gout, out, base, E, c, h);
+            acc, bcol, wv, bv, rb, cout, gout, out, base, E, c, h, st4, wc);
     }
 }
 
-template <bool KEEP, bool HAS_W, bool HAS_BASE>
+template <bool KEEP, int HAS_W, bool HAS_BASE>
 __global__ __launch_bounds__(256, 3)
 void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
                           const float* __restrict__ w2c,   // [64,64] in x out
                           const float* __restrict__ w2g,
                           const float* __restrict__ b2c,   // [64]
                           const float* __restrict__ b2g,
-                          const float* __restrict__ w,     // [E,64], HAS_W
+                          const float* __restrict__ w,     // [E,64], HAS_W;
+                                                           // 2: bexp [E,9]
                           const float* __restrict__ bs,    // [E,64], HAS_BASE
                           float* __restrict__ cout,        // [E,64], KEEP
                           float* __restrict__ gout,        // [E,64], KEEP
                           float* __restrict__ out,         // [E,64]
-                          int64_t E) {
+                          int64_t E,
+                          // HAS_W == 2 only
+                          const float* __restrict__ fwW,   // [64,9]
+                          const float* __restrict__ fwmask) {  // [E] or null
     __shared__ float4 wlds[64 * 32];
+    __shared__ float4 wl9[HAS_W == 2 ? 64 * RBF_PAD / 4 : 1];
+    __shared__ float4 bst[HAS_W == 2 ? (BLOCK / 64) * RBF_TILE / 4 : 1];
+    if (HAS_W == 2) radial_stage_W((float*)wl9, fwW);
     for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
         const int k = i >> 5, col = i & 31;
         wlds[i] = make_float4(w2c[k * 64 + col], w2c[k * 64 + 32 + col],
@@ -1246,6 +1446,8 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
         const int64_t r = base + c;
         const int64_t lrow = r < E ? r : E - 1;   // clamp, never read past E
         const float4* ap = (const float4*)(hp + lrow * 128) + h;
+        float sv[6];
+        if (HAS_W == 2) radial_tile_load(sv, w, fwmask, base, E, lane_t);
         float4 alo[8], ahi[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -1253,6 +1455,9 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
             ahi[i] = ap[16 + 2 * i];
         }
         __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
+        float* st = (float*)bst + wave * RBF_TILE;
+        if (HAS_W == 2) radial_tile_store(st, sv, lane_t);
+        const float4* st4 = (const float4*)st + (4 * h) * (RBF_PAD / 4);
         f32x16 acc[4];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
@@ -1275,10 +1480,10 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
         __builtin_amdgcn_s_setprio(0);
         if (base + 32 <= E)
             mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, true>(
-                acc, bcol, w, bs, cout, gout, out, base, E, c, h);
+                acc, bcol, w, bs, cout, gout, out, base, E, c, h, wl9, st4);
         else
             mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, false>(
-                acc, bcol, w, bs, cout, gout, out, base, E, c, h);
+                acc, bcol, w, bs, cout, gout, out, base, E, c, h, wl9, st4);
     }
 }
 
@@ -1326,6 +1531,9 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
 // 66048 B LDS, 2 waves/SIMD, no scratch.  The three-gather variants sit 1-7
 // registers under the 256 of two waves per SIMD: check these remarks after
 // any change here or in the compiler, a spill would not show otherwise.
+// The four factored-w variants <2, KEEP, true, 2, HAS_BASE>
+// (dm_gated_mlp3_fw_f32): 243-256 VGPR (256: no-keep with base), 0 AGPR,
+// 60-92 SGPR, 75264 B LDS, 2 waves/SIMD, no scratch.
 // 384-thread blocks (3 waves/SIMD) would need <= 168 VGPR, i.e. none of the
 // look-ahead; not built.
 // Stand-alone at 46M rows (tests/perf_gated_mlp_fused.py, median of 5, ms;
@@ -1362,6 +1570,12 @@ inline int gated_mlp_blocks(int64_t rows) {
     const int64_t tiles = (rows + 31) / 32;         // one 32-row tile per wave
     const int64_t b = (tiles + BLOCK / 64 - 1) / (BLOCK / 64);
     return (int)(b < 1 ? 1 : (b > GATED_MLP_MAX_BLOCKS ? GATED_MLP_MAX_BLOCKS : b));
+}
+
+// grid of the factored reverse tail: the cap of its resident blocks per CU
+inline int mlp_tail_bwd_fw_blocks(int64_t rows) {
+    return DM_FW_BWD_WAVES == 2 ? gated_mlp_blocks(rows)
+                                : edge_mlp_blocks(rows);
 }
 
 // The lane's own slices of one half (HALF 0: z columns 0-63, 1: 64-127) of
@@ -1418,7 +1632,7 @@ __device__ __forceinline__ void gated_mlp_interleave() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int NGATHER, bool KEEP, bool OUT, bool HAS_W, bool HAS_BASE>
+template <int NGATHER, bool KEEP, bool OUT, int HAS_W, bool HAS_BASE>
 __global__ __launch_bounds__(256, 2)
 void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
                     const float* __restrict__ WT,    // [64,128] row-major
@@ -1433,17 +1647,24 @@ void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
                     const float* __restrict__ w2g,
                     const float* __restrict__ b2c,   // [64]
                     const float* __restrict__ b2g,
-                    const float* __restrict__ w,     // [E,64], HAS_W
+                    const float* __restrict__ w,     // [E,64], HAS_W;
+                                                     // 2: bexp [E,9]
                     const float* __restrict__ bs,    // [E,64], HAS_BASE
                     float* __restrict__ zout,        // [E,128], KEEP
                     float* __restrict__ cout,        // [E,64], KEEP
                     float* __restrict__ gout,        // [E,64], KEEP
                     float* __restrict__ out,         // [E,64], OUT
-                    int64_t E) {
+                    int64_t E,
+                    // HAS_W == 2 only
+                    const float* __restrict__ fwW,   // [64,9]
+                    const float* __restrict__ fwmask) {  // [E] or null
     // the two parents' LDS images, unchanged
     __shared__ float4 wl1[64 * 32];
     __shared__ float4 wl2[64 * 32];
     __shared__ float4 bias4[32];
+    __shared__ float4 wl9[HAS_W == 2 ? 64 * RBF_PAD / 4 : 1];
+    __shared__ float4 bst[HAS_W == 2 ? (BLOCK / 64) * RBF_TILE / 4 : 1];
+    if (HAS_W == 2) radial_stage_W((float*)wl9, fwW);
     for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) {
         const int k = i >> 5, col = i & 31;
         const float* p = WT + k * 128 + col;
@@ -1564,7 +1785,8 @@ void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
             gated_mlp_interleave();
         }
         // w and base of all 16 accumulator rows fly during the last MFMA run
-        float wv[16][2], bv[16][2];
+        float wv[16][2], bv[16][2], sv[6];
+        if (HAS_W == 2) radial_tile_load(sv, w, fwmask, base, E, lane_t);
         // (always the clamping form: a branch to the unclamped one on full
         // tiles spills, 96-344 B of scratch in six variants)
         mlp_tail_fwd_loads<HAS_W, HAS_BASE, false, 16>(wv, bv, 0, w, bs, base,
@@ -1583,12 +1805,21 @@ void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
         }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
+        // factored w: the tile's bexp block into the wave's LDS region, the
+        // lane's two W rows out of the image
+        float* st = (float*)bst + wave * RBF_TILE;
+        float wc[2][N_RBF];
+        if (HAS_W == 2) {
+            radial_tile_store(st, sv, lane_t);
+            radial_lane_W(wc, wl9, c);
+        }
+        const float4* st4 = (const float4*)st + (4 * h) * (RBF_PAD / 4);
         if (base + 32 <= E)
             mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, true, OUT, 16>(
-                acc, bcol, wv, bv, 0, cout, gout, out, base, E, c, h);
+                acc, bcol, wv, bv, 0, cout, gout, out, base, E, c, h, st4, wc);
         else
             mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, false, OUT, 16>(
-                acc, bcol, wv, bv, 0, cout, gout, out, base, E, c, h);
+                acc, bcol, wv, bv, 0, cout, gout, out, base, E, c, h, st4, wc);
         if (!more) break;
         tile = next;
     }
@@ -2197,20 +2428,24 @@ __global__ void k_rot_dD(const float* __restrict__ go,
 
 
 // dm_gated_mlp_tail_fwd_f32's launch, by variant
-template <bool KEEP, bool HAS_W>
+template <bool KEEP, int HAS_W>
 static void launch_mlp_tail_fwd(const float* h, const float* w2c,
                                 const float* w2g, const float* b2c,
                                 const float* b2g, const float* w,
                                 const float* base, float* c_out, float* g_out,
-                                float* out, int64_t E, hipStream_t s) {
+                                float* out, int64_t E, hipStream_t s,
+                                const float* fwW = nullptr,
+                                const float* fwmask = nullptr) {
     if (base)
         k_gated_mlp_tail_fwd<KEEP, HAS_W, true>
             <<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-                h, w2c, w2g, b2c, b2g, w, base, c_out, g_out, out, E);
+                h, w2c, w2g, b2c, b2g, w, base, c_out, g_out, out, E, fwW,
+                fwmask);
     else
         k_gated_mlp_tail_fwd<KEEP, HAS_W, false>
             <<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-                h, w2c, w2g, b2c, b2g, w, nullptr, c_out, g_out, out, E);
+                h, w2c, w2g, b2c, b2g, w, nullptr, c_out, g_out, out, E, fwW,
+                fwmask);
 }
 
 // dm_gated_mlp3/4_f32: checks and launch, by form
@@ -2222,7 +2457,9 @@ static int gated_mlp_run(const float* erow, const float* WT, const float* bias,
                          const float* b2c, const float* b2g, const float* w,
                          const float* base, float* z_out, float* c_out,
                          float* g_out, float* out, int64_t E, int64_t Din,
-                         int64_t d, hipStream_t s) {
+                         int64_t d, hipStream_t s,
+                         const float* fwW = nullptr,
+                         const float* fwmask = nullptr) {
     if (Din != 64 || d != 64) {
         g_err = "gated_mlp fused kernel is compiled for Din=64, d=64";
         return -1;
@@ -2254,12 +2491,28 @@ static int gated_mlp_run(const float* erow, const float* WT, const float* bias,
         g_err = "gated_mlp: erow, the gather tables and z_out must be 16-byte aligned";
         return -1;
     }
+    // factored w: w is bexp [E,9]; the two-gather forms with out only
+    if (fwW && (NGATHER != 2 || !w || !out)) {
+        g_err = "gated_mlp: the factored-w form is the two-gather one with "
+                "bexp and out";
+        return -1;
+    }
     if (E <= 0) return 0;
     const int grid = gated_mlp_blocks(E);
 #define DM_GMLP_LAUNCH(KEEP, OUT, HW, HB)                                    \
     k_gated_mlp_64<NGATHER, KEEP, OUT, HW, HB><<<grid, BLOCK, 0, s>>>(       \
         erow, WT, bias, g0, g1, g2, i0, i1, i2, w2c, w2g, b2c, b2g, w, base, \
-        z_out, c_out, g_out, out, E)
+        z_out, c_out, g_out, out, E, fwW, fwmask)
+    if constexpr (NGATHER == 2) {
+        if (fwW) {
+            if (z_out && base) DM_GMLP_LAUNCH(true, true, 2, true);
+            else if (z_out) DM_GMLP_LAUNCH(true, true, 2, false);
+            else if (base) DM_GMLP_LAUNCH(false, true, 2, true);
+            else DM_GMLP_LAUNCH(false, true, 2, false);
+            DM_CHECK_LAUNCH();
+            return 0;
+        }
+    }
 #define DM_GMLP_WB(KEEP)                                                     \
     do {                                                                     \
         if (w && base) DM_GMLP_LAUNCH(KEEP, true, true, true);               \
@@ -2450,11 +2703,13 @@ int dm_gated_mlp_tail_bwd_f32(const float* go, const float* c, const float* g,
     }
     if (E <= 0) return 0;
     if (w)
-        k_gated_mlp_tail_bwd<true, false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-            go, nullptr, c, g, w, z, w2c, w2g, dz, dw, E);
+        k_gated_mlp_tail_bwd<1, false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, nullptr, c, g, w, z, w2c, w2g, dz, dw, E, nullptr, nullptr,
+            nullptr, nullptr);
     else
-        k_gated_mlp_tail_bwd<false, false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-            go, nullptr, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
+        k_gated_mlp_tail_bwd<0, false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, nullptr, c, g, nullptr, z, w2c, w2g, dz, nullptr, E, nullptr,
+            nullptr, nullptr, nullptr);
     DM_CHECK_LAUNCH();
     return 0;
 }
@@ -2480,11 +2735,43 @@ int dm_gated_mlp_tail_bwd_idx_f32(const float* go, const int32_t* idx,
     }
     if (E <= 0) return 0;
     if (w)
-        k_gated_mlp_tail_bwd<true, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-            go, idx, c, g, w, z, w2c, w2g, dz, dw, E);
+        k_gated_mlp_tail_bwd<1, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, idx, c, g, w, z, w2c, w2g, dz, dw, E, nullptr, nullptr, nullptr,
+            nullptr);
     else
-        k_gated_mlp_tail_bwd<false, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
-            go, idx, c, g, nullptr, z, w2c, w2g, dz, nullptr, E);
+        k_gated_mlp_tail_bwd<0, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+            go, idx, c, g, nullptr, z, w2c, w2g, dz, nullptr, E, nullptr,
+            nullptr, nullptr, nullptr);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp_tail_bwd_fw_f32(const float* go, const int32_t* idx,
+                                 const float* c, const float* g,
+                                 const float* bexp, const float* W,
+                                 const float* mask, const float* z,
+                                 const float* w2c, const float* w2g,
+                                 float* dz, const float* dbexp_in,
+                                 float* dbexp, int64_t E, int64_t d,
+                                 int64_t n_rbf, uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64 || n_rbf != N_RBF) {
+        g_err = "gated_mlp_tail_bwd_fw is compiled for d=64, n_rbf=9";
+        return -1;
+    }
+    if (!bexp || !W || !dbexp) {
+        g_err = "gated_mlp_tail_bwd_fw: bexp, W and dbexp must be given";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    if (idx)
+        k_gated_mlp_tail_bwd<2, true><<<mlp_tail_bwd_fw_blocks(E), BLOCK, 0, s>>>(
+            go, idx, c, g, bexp, z, w2c, w2g, dz, nullptr, E, W, mask,
+            dbexp_in, dbexp);
+    else
+        k_gated_mlp_tail_bwd<2, false><<<mlp_tail_bwd_fw_blocks(E), BLOCK, 0, s>>>(
+            go, nullptr, c, g, bexp, z, w2c, w2g, dz, nullptr, E, W, mask,
+            dbexp_in, dbexp);
     DM_CHECK_LAUNCH();
     return 0;
 }
@@ -2538,6 +2825,57 @@ int dm_gated_mlp_tail_fwd_f32(const float* h, const float* w2c,
     }
     DM_CHECK_LAUNCH();
     return 0;
+}
+
+int dm_gated_mlp_tail_fwd_fw_f32(const float* h, const float* w2c,
+                                 const float* w2g, const float* b2c,
+                                 const float* b2g, const float* bexp,
+                                 const float* W, const float* mask,
+                                 const float* base, float* c_out,
+                                 float* g_out, float* out, int64_t E,
+                                 int64_t d, int64_t n_rbf, uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64 || n_rbf != N_RBF) {
+        g_err = "gated_mlp_tail_fwd_fw is compiled for d=64, n_rbf=9";
+        return -1;
+    }
+    if ((c_out == nullptr) != (g_out == nullptr)) {
+        g_err = "gated_mlp_tail_fwd_fw: c_out and g_out must be given together";
+        return -1;
+    }
+    if (!bexp || !W) {
+        g_err = "gated_mlp_tail_fwd_fw: bexp and W must be given";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    if (c_out) launch_mlp_tail_fwd<true, 2>(h, w2c, w2g, b2c, b2g, bexp, base,
+                                            c_out, g_out, out, E, s, W, mask);
+    else launch_mlp_tail_fwd<false, 2>(h, w2c, w2g, b2c, b2g, bexp, base,
+                                       nullptr, nullptr, out, E, s, W, mask);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp3_fw_f32(const float* erow, const float* WT, const float* bias,
+                         const float* zs, const float* zd, const int32_t* src,
+                         const int32_t* dst, const float* w2c,
+                         const float* w2g, const float* b2c, const float* b2g,
+                         const float* bexp, const float* W, const float* mask,
+                         const float* base, float* z_out, float* c_out,
+                         float* g_out, float* out, int64_t E, int64_t Din,
+                         int64_t d, int64_t n_rbf, uint64_t stream) {
+    if (n_rbf != N_RBF) {
+        g_err = "gated_mlp3_fw is compiled for n_rbf=9";
+        return -1;
+    }
+    if (!bexp || !W) {
+        g_err = "gated_mlp3_fw: bexp and W must be given";
+        return -1;
+    }
+    return gated_mlp_run<2>(erow, WT, bias, zs, zd, nullptr, src, dst, nullptr,
+                            w2c, w2g, b2c, b2g, bexp, base, z_out, c_out,
+                            g_out, out, E, Din, d, (hipStream_t)stream, W,
+                            mask);
 }
 
 int dm_gated_mlp3_f32(const float* erow, const float* WT, const float* bias,

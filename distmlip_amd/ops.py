@@ -82,6 +82,19 @@ def hip_lib() -> ctypes.CDLL:
                                           fp, fp, fp, fp, fp, fp, fp, fp, fp,
                                           fp, c_int64, c_int64, c_int64,
                                           c_uint64]
+        # factored message weight (RadialW): bexp, W, mask in place of w
+        lib.dm_gated_mlp_tail_fwd_fw_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_fwd_fw_f32.argtypes = [
+            fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, c_int64, c_int64,
+            c_int64, c_uint64]
+        lib.dm_gated_mlp3_fw_f32.restype = c_int32
+        lib.dm_gated_mlp3_fw_f32.argtypes = [
+            fp, fp, fp, fp, fp, ip, ip, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp,
+            fp, fp, c_int64, c_int64, c_int64, c_int64, c_uint64]
+        lib.dm_gated_mlp_tail_bwd_fw_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_bwd_fw_f32.argtypes = [
+            fp, ip, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, c_int64,
+            c_int64, c_int64, c_uint64]
         lib.dm_mace_tp_fwd_f32.restype = c_int32
         lib.dm_mace_tp_fwd_f32.argtypes = [fp, fp, fp, fp, ip, fp, c_int32,
                                            fp, fp, fp, fp, c_int64, c_int32,
@@ -608,13 +621,88 @@ class _GatedCombinePacked(torch.autograd.Function):
         return dcg, dw, (go if ctx.has_base else None)
 
 
+class RadialW:
+    """A shared message weight in factored form, accepted wherever
+    HipOps.mlp_tail_act, r_mlp_tail_fwd, r_gated_mlp3 and r_mlp_tail_bwd take
+    a dense w [E,d]:
+        w = (bexp @ W.t()) * mask
+    with bexp [E,n_rbf], W [d,n_rbf] and mask [E] (or [E,1]) or None.  The
+    kernels compute w where they use it (one fixed fp32 order, the same bits
+    in all of them) and the dense array never exists.  r_mlp_tail_bwd then
+    returns (dz, dbexp) instead of (dz, dw), with dbexp = (dw * mask) @ W
+    added onto dbexp_acc in place when that is given."""
+
+    __slots__ = ("bexp", "W", "mask", "dbexp_acc")
+
+    def __init__(self, bexp, W, mask=None, dbexp_acc=None):
+        self.bexp, self.W, self.dbexp_acc = bexp, W, dbexp_acc
+        self.mask = mask.reshape(-1) if mask is not None else None
+
+    @property
+    def requires_grad(self):
+        return self.bexp.requires_grad
+
+    def with_acc(self, dbexp_acc):
+        return RadialW(self.bexp, self.W, self.mask, dbexp_acc)
+
+    def check(self, E, d):
+        _chk_f32(self.bexp, self.W, self.mask, self.dbexp_acc)
+        assert self.bexp.shape[0] == E and self.W.shape == (
+            d, self.bexp.shape[1])
+        assert self.mask is None or self.mask.shape == (E,)
+        assert self.dbexp_acc is None \
+            or self.dbexp_acc.shape == self.bexp.shape
+
+    def ptrs(self):
+        return (_fp(self.bexp), _fp(self.W),
+                _fp(self.mask) if self.mask is not None else None)
+
+
+def use_factored_w() -> bool:
+    """Factored message weights switch: DM_NO_FACTORED_W=1 restores the dense
+    [E,d] weights (bexp @ W.t() by rocBLAS) everywhere, for A/B runs in one
+    build."""
+    return os.environ.get("DM_NO_FACTORED_W", "0") != "1"
+
+
+def _raw_mlp_tail_bwd_fw(go, cg, rw, z, w2, go_idx):
+    """raw_mlp_tail_bwd with a RadialW: (dz, dbexp)."""
+    _chk_f32(go, cg, z, w2)
+    d = go.shape[1]
+    E = go.shape[0] if go_idx is None else go_idx.shape[0]
+    assert cg.shape == (2, E, d) and z.shape == (E, 2 * d)
+    assert w2.shape == (2, d, d)
+    rw.check(E, d)
+    if go_idx is not None:
+        assert go_idx.dtype == torch.int32 and go_idx.is_contiguous() \
+            and go_idx.device == go.device
+    half = E * d
+    dz = torch.empty_like(z)
+    acc = rw.dbexp_acc
+    dbexp = acc if acc is not None else torch.empty_like(rw.bexp)
+    bexp_p, W_p, mask_p = rw.ptrs()
+    _check(hip_lib().dm_gated_mlp_tail_bwd_fw_f32(
+        _fp(go), _ip(go_idx) if go_idx is not None else None,
+        ctypes.cast(cg.data_ptr(), POINTER(c_float)),
+        ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
+        bexp_p, W_p, mask_p, _fp(z),
+        ctypes.cast(w2.data_ptr(), POINTER(c_float)),
+        ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
+        _fp(dz), _fp(acc) if acc is not None else None, _fp(dbexp), E, d,
+        rw.bexp.shape[1], _stream()), "dm_gated_mlp_tail_bwd_fw_f32")
+    return dz, dbexp
+
+
 def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None):
     """(dz, dw) of one gated MLP's tail in ONE kernel: the reverse of
     out = base + silu(cg[0]) * sigmoid(cg[1]) * w with cg = the second layer
     over silu(z).  go [E,d], cg [2,E,d] packed, w [E,d] or None, z [E,2d],
     w2 [2,d,d] (input x output per half).  d must be 64.  With go_idx
     (int32 [E]) go is a [N,d] table and row r takes go[go_idx[r]]: the
-    result on the materialized go[go_idx], without that gather."""
+    result on the materialized go[go_idx], without that gather.
+    w may be a RadialW: (dz, dbexp) is returned then."""
+    if isinstance(w, RadialW):
+        return _raw_mlp_tail_bwd_fw(go, cg, w, z, w2, go_idx)
     _chk_f32(go, cg, w, z, w2)
     d = go.shape[1]
     E = go.shape[0] if go_idx is None else go_idx.shape[0]
@@ -659,7 +747,10 @@ def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
     sigmoid(cg[1]) * w.  h [E,2d], w2 [2,d,d] (input x output per half),
     b2 [2,1,d], w and base [E,d] or None.  cg [2,E,d] packed is written and
     returned only with keep_cg; out is the same bit for bit either way.
-    d must be 64."""
+    d must be 64.  w may be a RadialW."""
+    rw = w if isinstance(w, RadialW) else None
+    if rw is not None:
+        w = None
     _chk_f32(h, w2, b2, w, base)
     E, d = h.shape[0], w2.shape[1]
     assert h.shape == (E, 2 * d) and w2.shape == (2, d, d)
@@ -670,6 +761,20 @@ def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
     out = torch.empty(E, d, dtype=h.dtype, device=h.device)
     cg = torch.empty(2, E, d, dtype=h.dtype, device=h.device) \
         if keep_cg else None
+    if rw is not None:
+        rw.check(E, d)
+        _check(hip_lib().dm_gated_mlp_tail_fwd_fw_f32(
+            _fp(h), ctypes.cast(w2.data_ptr(), POINTER(c_float)),
+            ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
+            ctypes.cast(b2.data_ptr(), POINTER(c_float)),
+            ctypes.cast(b2.data_ptr() + 4 * d, POINTER(c_float)),
+            *rw.ptrs(), _fp(base) if base is not None else None,
+            ctypes.cast(cg.data_ptr(), POINTER(c_float)) if keep_cg else None,
+            ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float))
+            if keep_cg else None,
+            _fp(out), E, d, rw.bexp.shape[1], _stream()),
+            "dm_gated_mlp_tail_fwd_fw_f32")
+        return out, cg
     _check(hip_lib().dm_gated_mlp_tail_fwd_f32(
         _fp(h), ctypes.cast(w2.data_ptr(), POINTER(c_float)),
         ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
@@ -697,7 +802,11 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
     and the combine, without the h [E,128] array between them.  Returns
     (z, cg, out): z [E,128] and cg [2,E,64] packed with keep, else None; out
     None with want_out=False (keep only; w and base are then not read).
-    Values are the two-kernel path's bit for bit."""
+    Values are the two-kernel path's bit for bit.  w may be a RadialW (two
+    tables, with out)."""
+    rw = w if isinstance(w, RadialW) and want_out else None
+    if isinstance(w, RadialW):
+        w = None
     _chk_f32(row, wt, bias, *tables, w2, b2, w, base)
     E, d = row.shape[0], w2.shape[1]
     assert wt.shape == (d, 2 * d) and w2.shape == (2, d, d)
@@ -728,6 +837,15 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
             _fp(z) if keep else None,
             at(cg) if keep else None, at(cg, 4 * half) if keep else None,
             _fp(out) if want_out else None, E, wt.shape[0], d, _stream())
+    if rw is not None:
+        assert len(tables) == 2, "a factored w takes the two-gather form"
+        rw.check(E, d)
+        tail = tail[:4] + rw.ptrs() + tail[5:-1] + (rw.bexp.shape[1],
+                                                    _stream())
+        _check(hip_lib().dm_gated_mlp3_fw_f32(
+            _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
+            _ip(idx[0]), _ip(idx[1]), *tail), "dm_gated_mlp3_fw_f32")
+        return z, cg, out
     if len(tables) == 2:
         _check(hip_lib().dm_gated_mlp3_f32(
             _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
@@ -803,6 +921,7 @@ class HipOps:
 
     is_reference = False
     tail_bwd_indexed = True      # r_mlp_tail_bwd takes go_idx
+    factored_w = True            # the w of the MLP tails may be a RadialW
 
     def gather(self, x, idx, csr=None):
         if csr is None:
@@ -865,9 +984,10 @@ class HipOps:
         assert not (torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (h, w, base))), \
             "mlp_tail_act is the no-grad form; use mlp_tail"
+        if not isinstance(w, RadialW):
+            w = w.contiguous() if w is not None else None
         return raw_mlp_tail_fwd(
-            h.contiguous(), w2, b2,
-            w.contiguous() if w is not None else None,
+            h.contiguous(), w2, b2, w,
             base.contiguous() if base is not None else None, False)[0]
 
     def scatter_edges(self, msg, pd, base=None):
@@ -928,7 +1048,7 @@ class HipOps:
     def r_mlp_tail_bwd(self, go, cg, w, z, w2, go_idx=None):
         """(dz, dw): r_combine_bwd + second-layer reverse + r_silu_bwd in
         one kernel (d = 64 only).  go_idx: go is a node table read by index
-        (r_gather_dst folded in)."""
+        (r_gather_dst folded in).  With w a RadialW: (dz, dbexp)."""
         return raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx)
 
     def r_edge_mlp3(self, erow, wt, bias, zs, zd, pd):

@@ -99,6 +99,17 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             entry dm_gated_mlp4_f32 only:
                                             bond_fwd / angle_fwd run their
                                             first layer through rocBLAS)
+    factored_w = True (class attribute)  -> OPTIONAL (HipOps, d = 64, n_rbf =
+                                            9): mlp_tail_act, r_mlp_tail_fwd,
+                                            r_gated_mlp3 and r_mlp_tail_bwd
+                                            take an ops.RadialW (bexp, W,
+                                            mask) as w and compute w = mask *
+                                            (bexp @ W.t()) in the kernel;
+                                            r_mlp_tail_bwd then returns (dz,
+                                            dbexp), added onto the RadialW's
+                                            dbexp_acc in place when given.
+                                            conv builds the dense w where a
+                                            backend lacks it
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

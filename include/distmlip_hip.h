@@ -193,6 +193,50 @@ int dm_gated_mlp4_f32(const float* arow, const float* WT, const float* bias,
                       float* c_out, float* g_out, float* out, int64_t L,
                       int64_t Din, int64_t d, uint64_t stream);
 
+/* Factored message weight.  The three entries below are
+ * dm_gated_mlp_tail_fwd_f32, dm_gated_mlp3_f32 and dm_gated_mlp_tail_bwd_f32
+ * (plain, or indexed with idx != NULL) with the dense w [E,d] replaced by its
+ * factors:
+ *   w[e][col] = (mask ? mask[e] : 1) * sum_k bexp[e][k] * W[col][k]
+ * bexp [E,n_rbf], W [d,n_rbf] row-major, mask [E] or NULL.  No dense [E,d]
+ * weight is read or written.  The sum has one fp32 order in all three:
+ * bexp[e][0] * W[col][0], then fmaf over k = 1..8 ascending, then the mask; the
+ * three kernels therefore see the same w bit for bit.  Outputs that do not
+ * depend on w (c, g, z) are the dense entries' bit for bit.
+ * The reverse entry returns, in place of dw,
+ *   dbexp[e][k] = mask[e] * sum_col dw[e][col] * W[col][k]  (+ dbexp_in[e][k])
+ * summed as: fmaf over the columns 8i+4h+t ascending for each half h = 0, 1
+ * of the row's columns (i = 0..7, t = 0..3), then half 0 + half 1, then the
+ * mask, then + dbexp_in, each step rounded.  dbexp_in [E,n_rbf] may be NULL
+ * and may be dbexp itself (accumulation in place).
+ * Compiled for d = 64 and n_rbf = 9 (dm_gated_mlp3_fw_f32: Din = 64 too);
+ * anything else, a NULL bexp, W or dbexp, returns an error and launches
+ * nothing.  Rows >= E are neither loaded nor stored.  dm_gated_mlp3_fw_f32
+ * takes the no-keep and the keep form, both with out. */
+int dm_gated_mlp_tail_fwd_fw_f32(const float* h, const float* w2c,
+                                 const float* w2g, const float* b2c,
+                                 const float* b2g, const float* bexp,
+                                 const float* W, const float* mask,
+                                 const float* base, float* c_out,
+                                 float* g_out, float* out, int64_t E,
+                                 int64_t d, int64_t n_rbf, uint64_t stream);
+int dm_gated_mlp3_fw_f32(const float* erow, const float* WT, const float* bias,
+                         const float* zs, const float* zd, const int32_t* src,
+                         const int32_t* dst, const float* w2c,
+                         const float* w2g, const float* b2c, const float* b2g,
+                         const float* bexp, const float* W, const float* mask,
+                         const float* base, float* z_out, float* c_out,
+                         float* g_out, float* out, int64_t E, int64_t Din,
+                         int64_t d, int64_t n_rbf, uint64_t stream);
+int dm_gated_mlp_tail_bwd_fw_f32(const float* go, const int32_t* idx,
+                                 const float* c, const float* g,
+                                 const float* bexp, const float* W,
+                                 const float* mask, const float* z,
+                                 const float* w2c, const float* w2g,
+                                 float* dz, const float* dbexp_in,
+                                 float* dbexp, int64_t E, int64_t d,
+                                 int64_t n_rbf, uint64_t stream);
+
 /* Fused edge geometry + radial basis (replaces the torch chain for
  * chgnet.py:96-124): per local edge e,
  *   bv[e]  = pos[dst[e]] + offshift[e] - pos[src[e]]
