@@ -24,6 +24,10 @@ Checkpointed steps (si1m) take _AtomBlockFn instead: the same atom_fwd /
 atom_bwd inside a node that recomputes itself, with the fused first layer,
 its reverse kernel (gradient sums in the epilogue) and the indexed reverse
 tail; 1205-1210 -> 1096-1102 ms/step at si1m (profiles/first_bwd_*).
+Their final block keeps its saves (_AtomBlockKeepFn), and the 4M rows that
+move between e and n around every bond block go through edge_to_bond /
+bond_to_edge, in place over e (1011-1014 -> 909-914 ms/step,
+profiles/row_exchange_*).
 """
 from __future__ import annotations
 
@@ -516,24 +520,42 @@ class _AtomBlockFn(torch.autograd.Function):
         assert not (Wbb.requires_grad or Wab.requires_grad
                     or pe[0].requires_grad or pn[0].requires_grad)
         wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
+        ctx.set_materialize_grads(False)
+        ctx.consts = (Wbb, Wab, edge_mask, pd, ops, pe, pn, d)
+        ctx.kept = None
+        if getattr(ctx, "keep", False):
+            # _AtomBlockKeepFn: the keep-form forward the backward would
+            # have re-run.  z and cg are neither inputs nor outputs; they
+            # hang on ctx as a plain list, which atom_bwd empties as it
+            # goes, so each is freed once consumed (saved tensors would
+            # all live until the backward returns)
+            v2, e2, saved = atom_fwd(ops, pd, v.detach(), e.detach(), wbb,
+                                     wab, pe, pn, d)
+            ctx.kept = list(saved)
+            ctx.save_for_backward(bexp)
+            return v2, e2
         # grad mode is off here, but v and e still carry requires_grad, by
         # which the first-layer Function decides whether to store z:
         # detached, both MLPs take the no-z form
         v2, e2 = _lean_atom(ops, pd, v.detach(), e.detach(), wbb, wab, pe,
                             pn, d)
-        ctx.set_materialize_grads(False)
         ctx.save_for_backward(v, e, bexp)
-        ctx.consts = (Wbb, Wab, edge_mask, pd, ops, pe, pn, d)
         return v2, e2
 
     @staticmethod
     def backward(ctx, go_v2, go_e2):
-        v, e, bexp = ctx.saved_tensors
         Wbb, Wab, edge_mask, pd, ops, pe, pn, d = ctx.consts
         with torch.no_grad():
-            wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
-            saved = list(atom_fwd(ops, pd, v, e, wbb, wab, pe, pn, d,
-                                  saves_only=True)[2])
+            if getattr(ctx, "keep", False):
+                assert ctx.kept, "a keep block runs its backward once"
+                bexp, = ctx.saved_tensors
+                saved, ctx.kept = ctx.kept, None
+                wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
+            else:
+                v, e, bexp = ctx.saved_tensors
+                wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
+                saved = list(atom_fwd(ops, pd, v, e, wbb, wab, pe, pn, d,
+                                      saves_only=True)[2])
             gv, ge, dwbb, dwab = atom_bwd(
                 ops, pd, saved, pe, pn, d, wbb, wab, go_v2, go_e2,
                 need_gv=ctx.needs_input_grad[0])
@@ -552,6 +574,141 @@ class _AtomBlockFn(torch.autograd.Function):
                     dbexp.addmm_(dwab, Wab)
         return (gv, ge, dbexp, None, None, None, None, None, None, None,
                 None)
+
+
+class _AtomBlockKeepFn(_AtomBlockFn):
+    """_AtomBlockFn for the FINAL atom block of a checkpointed step: its
+    backward starts as soon as the readout is done, so dropping z / cg only
+    to recompute them buys nothing.  The forward runs in keep form (atom_fwd,
+    same packs and factored weights, outputs bit for bit the lean form's)
+    and the backward goes straight to atom_bwd.  Same arguments; it runs
+    through _AtomBlockFn.forward with a flag on ctx."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.keep = True
+        return _AtomBlockFn.forward(ctx, *args)
+
+
+def final_keep_enabled() -> bool:
+    """DM_NO_FINAL_KEEP=1 gives the final block back its recomputation."""
+    return os.environ.get("DM_NO_FINAL_KEEP", "0") != "1"
+
+
+# ---------------------------------------------------------------------------
+# edge <-> bond row exchange of a checkpointed step
+# ---------------------------------------------------------------------------
+
+def row_exchange_enabled() -> bool:
+    """DM_NO_ROW_EXCHANGE=1 restores the two out-of-place index_copy lines
+    of runtime.step."""
+    return os.environ.get("DM_NO_ROW_EXCHANGE", "0") != "1"
+
+
+def _native_rows(ops, *ts):
+    return hasattr(ops, "r_move_rows") and all(
+        t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def _move_rows(ops, src, si, dst, di, add=False):
+    """dst[di] (=|+=) src[si] by rows, in place over a dst the caller owns:
+    one kernel where the backend has r_move_rows, else torch index ops.
+    di is unique, so the add rounds once per element either way."""
+    if _native_rows(ops, src, dst):
+        ops.r_move_rows(src.contiguous(), si, dst, di, add)
+    elif add:
+        dst.index_add_(0, di, src.index_select(0, si))
+    else:
+        dst.index_copy_(0, di, src.index_select(0, si))
+
+
+def _zero_rows(ops, dst, di):
+    if _native_rows(ops, dst):
+        ops.r_zero_rows(dst, di)
+    else:
+        dst.index_fill_(0, di, 0)
+
+
+def _own(g):
+    """A contiguous copy of an incoming gradient, which is never written."""
+    return g.clone(memory_format=torch.contiguous_format)
+
+
+class _EdgeToBondFn(torch.autograd.Function):
+    """(e, n_prev) -> (e, n_c): n_c = n_prev.index_copy(map_ude, e[map_de]).
+
+    e is handed back as is and marked dirty, although nothing is written to
+    it: its history then runs block -> this -> bond_to_edge -> next block as
+    ONE consumer chain, and the backward receives the gradient of e and the
+    gradient of n_c together.  Left as two consumers of e (this gather and
+    the next user), autograd sums two dense [E,d] gradients of which one is
+    zero outside the 4M mapped rows, after building that one with a zero
+    fill, a sort and an index_put.  Here: one copy of G_e and one row kernel.
+    """
+
+    @staticmethod
+    def forward(ctx, e, n_prev, pd, ops):
+        B, M = n_prev.shape[0], len(pd.map_ude)
+        # map_ude is unique: with B == M it names every row
+        n_c = torch.empty_like(n_prev, memory_format=torch.contiguous_format) \
+            if B == M else _own(n_prev)
+        _move_rows(ops, e, pd.map_de, n_c, pd.map_ude)
+        ctx.mark_dirty(e)
+        ctx.set_materialize_grads(False)
+        ctx.pd, ctx.ops, ctx.e_shape = pd, ops, e.shape
+        return e, n_c
+
+    @staticmethod
+    def backward(ctx, G_e, G_nc):
+        pd, ops = ctx.pd, ctx.ops
+        if G_nc is None:
+            return G_e, None, None, None
+        ge = gn = None
+        if ctx.needs_input_grad[0]:
+            ge = _own(G_e) if G_e is not None else G_nc.new_zeros(ctx.e_shape)
+            _move_rows(ops, G_nc, pd.map_ude, ge, pd.map_de, add=True)
+        if ctx.needs_input_grad[1]:
+            gn = _own(G_nc)
+            _zero_rows(ops, gn, pd.map_ude)
+        return ge, gn, None, None
+
+
+class _BondToEdgeFn(torch.autograd.Function):
+    """(e, n2) -> e with e[map_de] = n2[map_ude], written IN PLACE over e
+    (the out-of-place index_copy clones all of e to change 4M rows)."""
+
+    @staticmethod
+    def forward(ctx, e, n2, pd, ops):
+        _move_rows(ops, n2, pd.map_ude, e, pd.map_de)
+        ctx.mark_dirty(e)
+        ctx.pd, ctx.ops, ctx.n_shape = pd, ops, n2.shape
+        return e
+
+    @staticmethod
+    def backward(ctx, go):
+        pd, ops = ctx.pd, ctx.ops
+        ge = gn2 = None
+        if ctx.needs_input_grad[1]:
+            full = ctx.n_shape[0] == len(pd.map_ude)
+            gn2 = go.new_empty(ctx.n_shape) if full \
+                else go.new_zeros(ctx.n_shape)
+            _move_rows(ops, go, pd.map_de, gn2, pd.map_ude)
+        if ctx.needs_input_grad[0]:
+            ge = _own(go)
+            _zero_rows(ops, ge, pd.map_de)
+        return ge, gn2, None, None
+
+
+def edge_to_bond(e, n_prev, pd, ops):
+    """(e, n_c) with n_c = n_prev.index_copy(0, pd.map_ude, e[pd.map_de]);
+    go on with the returned e (same storage) so that e keeps one consumer.
+    Only where no saved tensor aliases e: the checkpointed steps."""
+    return _EdgeToBondFn.apply(e, n_prev, pd, ops)
+
+
+def bond_to_edge(e, n2, pd, ops):
+    """e.index_copy(0, pd.map_de, n2[pd.map_ude]) written in place over e."""
+    return _BondToEdgeFn.apply(e, n2, pd, ops)
 
 
 def atom_block_available(ops, pe, d, dtype) -> bool:

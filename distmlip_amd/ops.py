@@ -168,6 +168,13 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_md_kick_reduce_f64.restype = c_int32
         lib.dm_md_kick_reduce_f64.argtypes = [dp, vp, c_int32, dp, cd, dp,
                                               dp, c_int64, c_uint64]
+        # indexed row moves (csrc/rows.hip): src, si, dst, di, M, D, op
+        lp = POINTER(c_int64)
+        lib.dm_move_rows_f32.restype = c_int32
+        lib.dm_move_rows_f32.argtypes = [fp, lp, fp, lp, c_int64, c_int64,
+                                         c_int32, c_uint64]
+        lib.dm_zero_rows_f32.restype = c_int32
+        lib.dm_zero_rows_f32.argtypes = [fp, lp, c_int64, c_int64, c_uint64]
         lib.dm_hip_last_error.restype = c_char_p
         _hip_lib = lib
     return _hip_lib
@@ -208,6 +215,49 @@ def raw_gather(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         _fp(x), _ip(idx), _fp(out), out.shape[0], x.shape[1], _stream()),
         "dm_gather_rows_f32")
     return out
+
+
+def _lp(t):
+    return ctypes.cast(t.data_ptr(), POINTER(c_int64)) if t is not None \
+        else None
+
+
+def _chk_rows(t, idx, M):
+    """t is a [R, D] fp32 device array; idx an int64 [M] device index into its
+    rows, or None for rows 0..M-1."""
+    _chk_f32(t)
+    assert t.dim() == 2
+    if idx is None:
+        assert M <= t.shape[0]
+    else:
+        assert idx.dtype == torch.int64 and idx.is_contiguous() \
+            and idx.device == t.device and idx.shape == (M,)
+
+
+def raw_move_rows(src, si, dst, di, add=False):
+    """dst[di[i]] (=|+=) src[si[i]] for every i, IN PLACE over dst, one
+    kernel.  si / di: int64 [M] or None for the identity; the entries of di
+    must be unique and every index a valid row (not checked: that would cost
+    a device round trip).  src and dst must not overlap."""
+    M = len(si) if si is not None else len(di) if di is not None \
+        else src.shape[0]
+    _chk_rows(src, si, M)
+    _chk_rows(dst, di, M)
+    assert src.shape[1] == dst.shape[1]
+    _check(hip_lib().dm_move_rows_f32(
+        _fp(src), _lp(si), _fp(dst), _lp(di), M, src.shape[1],
+        1 if add else 0, _stream()), "dm_move_rows_f32")
+    return dst
+
+
+def raw_zero_rows(dst, di, M=None):
+    """dst[di[i]] = 0 for every i, IN PLACE, one kernel; di None: the first
+    M rows."""
+    M = len(di) if di is not None else M
+    _chk_rows(dst, di, M)
+    _check(hip_lib().dm_zero_rows_f32(
+        _fp(dst), _lp(di), M, dst.shape[1], _stream()), "dm_zero_rows_f32")
+    return dst
 
 
 def raw_seg_sum(msg, row_ptr, n_rows, base=None):
@@ -1069,6 +1119,15 @@ class HipOps:
         """(gbase +) dz @ wt.t() in one kernel (wt = the [64,128] fusedT
         pack only); out may be gbase when the caller owns it."""
         return raw_edge_mlp_bwd(dz, wt, gbase, out)
+
+    def r_move_rows(self, src, si, dst, di, add=False):
+        """dst[di] (=|+=) src[si] by rows, in place over dst, one kernel;
+        si / di int64 or None (identity), di unique."""
+        return raw_move_rows(src, si, dst, di, add)
+
+    def r_zero_rows(self, dst, di):
+        """dst[di] = 0 by rows, in place, one kernel."""
+        return raw_zero_rows(dst, di)
 
     def r_mlp_tail_fwd(self, h, w2, b2, w, base):
         """(cg, out): second layer + r_combine_fwd in one kernel (d = 64

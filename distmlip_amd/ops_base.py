@@ -82,6 +82,18 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             the epilogue; out may be gbase.
                                             OPTIONAL (HipOps, wt [64,128]):
                                             conv falls back to addmm
+    r_move_rows(src, si, dst, di, add=False)
+                                         -> dst, written IN PLACE:
+                                            dst[di[i]] (=|+=) src[si[i]] by
+                                            whole rows in one kernel.  si / di
+                                            are int64 [M] (pd.map_de /
+                                            pd.map_ude) or None for the
+                                            identity; di must be unique.
+                                            OPTIONAL (HipOps, fp32): conv's
+                                            edge_to_bond / bond_to_edge fall
+                                            back to torch index ops
+    r_zero_rows(dst, di)                 -> dst with rows di zeroed IN PLACE.
+                                            OPTIONAL, with r_move_rows
     r_mlp_tail_fwd(h, w2, b2, w, base)   -> (cg, out): the second layer's
                                             batched GEMM and r_combine_fwd as
                                             one kernel.  OPTIONAL (HipOps,

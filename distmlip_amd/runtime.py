@@ -32,8 +32,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from distmlip_amd.conv import (_AtomBlockFn, _AtomConvFn, _BondConvFn,
-                               atom_block_available, conv_fn_available)
+from distmlip_amd.conv import (_AtomBlockFn, _AtomBlockKeepFn, _AtomConvFn,
+                               _BondConvFn, atom_block_available,
+                               bond_to_edge, conv_fn_available, edge_to_bond,
+                               final_keep_enabled, row_exchange_enabled)
 from distmlip_amd.chgnet import (
     PartitionData,
     _packed_weights,
@@ -434,6 +436,16 @@ class SpmdEngine:
         e = core.bond_embedding(bond_expansion)
 
         use_bg = self.use_bond_graph
+        d = cfg.dim
+        ckpt = self.checkpoint == "on" or (
+            self.checkpoint == "auto" and len(pd.src) > 10_000_000)
+        # checkpointed steps move the 4M mapped rows between e and n with the
+        # single-consumer Function pair of conv.py (in place over e); the
+        # unchecked op-by-op path keeps the out-of-place torch lines, since
+        # there an in-place write could meet a saved tensor
+        # (nor does the whole-graph Function, which does its own exchange)
+        row_x = (ckpt and use_bg and row_exchange_enabled()
+                 and _os.environ.get("DM_WHOLE_GRAPH_CKPT") != "1")
         if use_bg:
             # owned bond geometry from local edges; ghosts by one halo each
             # (reference chgnet.py:129-164).  map_ude is a permutation of
@@ -462,13 +474,12 @@ class SpmdEngine:
                 ops.gather(nd_vec, pd.l_src, csr=pd.line_src_csr),
                 ops.gather(nd_vec, pd.l_dst, csr=pd.line_dst_csr))
             a = core.angle_embedding(fourier_expansion(theta, core.angle_freq))
-            n = torch.empty(pd.n_bonds, cfg.dim, dtype=ft, device=dev).index_copy(
-                0, pd.map_ude, e[pd.map_de])
+            n = torch.empty(pd.n_bonds, cfg.dim, dtype=ft, device=dev)
+            if row_x:
+                e, n = edge_to_bond(e, n, pd, ops)
+            else:
+                n = n.index_copy(0, pd.map_ude, e[pd.map_de])
             n = _halo(n, line_plan)
-
-        d = cfg.dim
-        ckpt = self.checkpoint == "on" or (
-            self.checkpoint == "auto" and len(pd.src) > 10_000_000)
 
         def _ck(fn, *args):
             if ckpt:
@@ -524,7 +535,12 @@ class SpmdEngine:
                         and not (wbb_w.requires_grad or wab_w.requires_grad)
                         and (v.requires_grad or e.requires_grad
                              or bond_expansion.requires_grad)):
-                    return _AtomBlockFn.apply(
+                    # the final block's backward follows its forward at
+                    # once: it keeps its saves instead of recomputing them
+                    fn = _AtomBlockKeepFn if (
+                        layer_i == -1 and final_keep_enabled()) \
+                        else _AtomBlockFn
+                    return fn.apply(
                         v, e, bond_expansion, wbb_w, wab_w, edge_mask, pd,
                         ops, pe, _packed_weights(blk.node_mlp), d)
             return _ck(atom_conv_body,
@@ -574,7 +590,10 @@ class SpmdEngine:
         for layer_i in range(cfg.n_blocks - 1):           # chgnet.py:296-368
             v, e = atom_conv(layer_i, v, e)
             if use_bg:
-                n = n.index_copy(0, pd.map_ude, e[pd.map_de])   # edge_to_bond
+                if row_x:
+                    e, n = edge_to_bond(e, n, pd, ops)
+                else:
+                    n = n.index_copy(0, pd.map_ude, e[pd.map_de])  # edge_to_bond
                 n = _halo(n, line_plan)
                 v = _halo(v, plan)
 
@@ -605,7 +624,10 @@ class SpmdEngine:
                     return ops.scatter_lines(msg, pd, base=n)
 
                 n = _ck(bond_body, n, a, v, exp3)
-                e = e.index_copy(0, pd.map_de, n[pd.map_ude])    # bond_to_edge
+                if row_x:
+                    e = bond_to_edge(e, n, pd, ops)
+                else:
+                    e = e.index_copy(0, pd.map_de, n[pd.map_ude])  # bond_to_edge
 
                 if layer_i < cfg.n_blocks - 2:
                     # the LAST bond block's angle update is dead compute

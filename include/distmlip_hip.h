@@ -451,6 +451,29 @@ int dm_md_kick_reduce_f64(double* vel, const void* force, int32_t force_f64,
                           const double* inv_mass, double b, double* partials,
                           double* out5, int64_t N, uint64_t stream);
 
+/* ---- indexed row moves (distmlip_amd/csrc/rows.hip): the edge <-> bond
+ * exchange of a CHGNet step and its reverse, in place over dst ----
+ *
+ *   dm_move_rows_f32:  dst[di[i], :] (=|+=) src[si[i], :]   for i < M
+ *   dm_zero_rows_f32:  dst[di[i], :] = 0                    for i < M
+ *
+ * src and dst are row-major fp32 with D columns and must not overlap.  si and
+ * di are int64 [M] device arrays (the dtype of the builders' map_de /
+ * map_ude); either may be NULL for the identity (row i).  CALLER'S CONTRACT:
+ * every index is a valid row of its array, and the entries of di are unique;
+ * each destination element then has exactly one writer, no atomics are used
+ * and the add form rounds once per element.  op is 0 (assign) or 1 (add).
+ * Rows move as float4 when D % 4 == 0 and both pointers are 16-byte aligned,
+ * as single floats otherwise; all offsets are 64-bit (arrays past 2^31
+ * elements are fine).  M <= 0 returns 0 without a launch; D outside
+ * [1, 2^31), another op, or a NULL src / dst returns an error and launches
+ * nothing. */
+int dm_move_rows_f32(const float* src, const int64_t* si, float* dst,
+                     const int64_t* di, int64_t M, int64_t D, int32_t op,
+                     uint64_t stream);
+int dm_zero_rows_f32(float* dst, const int64_t* di, int64_t M, int64_t D,
+                     uint64_t stream);
+
 const char* dm_hip_last_error(void);
 
 #ifdef __cplusplus
