@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/distmlip_hip.h"
 
@@ -70,8 +71,238 @@ __global__ void k_gather_rows_s(const float* __restrict__ x,
     }
 }
 
-__device__ __forceinline__ float siluf(float x) {
+// ---------------------------------------------------------------------------
+// Exact sigmoid and SiLU.  Every CHGNet kernel in this file evaluates them
+// through sigf / siluf below, so all paths agree bit for bit.
+//
+// The defining expressions are the _ref forms: libm's expf and the IEEE
+// division.  hipcc -O3 turns one of them into 25 VALU instructions: 13 for
+// expf(-x) (v_mul, v_rndne, v_sub, v_fma, v_fmac, v_add, v_cvt_i32,
+// v_exp_f32, v_ldexp and two v_cmp/v_cndmask range selects), the 1.0f +, and
+// 11 for the division (two v_div_scale, v_rcp_f32, six fma/mul, v_div_fmas,
+// v_div_fixup).  For |x| <= 87 most of that guards operand ranges that cannot
+// occur: the range selects of expf fire only beyond 88.7 / 103.3, the divisor
+// 1 + exp(-x) lies in [1, 2^126) so nothing needs scaling or fixing up, and
+// one residual step on the hardware reciprocal already rounds correctly.
+// sigf and siluf are that short sequence:
+//   expf(-x) as libm computes it, minus the selects            9
+//   y = 1 + E                                                  1
+//   sigf:  r = rcp(y); r += (1 - y r) r                        3
+//   siluf: r = rcp(y); q = x r; q += (x - y q) r               4
+//   |x| <= 87 test (v_cmp; the branch is scalar)               1
+// = 14 and 15 VALU instructions.  If any active lane of the wave fails the
+// test (large |x|, infinities, NaN) the whole wave evaluates the _ref form
+// instead: there exp(-x) under- or overflows, the reciprocal is subnormal and
+// the short division is not exact.  The branch is wave-uniform.
+// Both return the bits of their _ref form for every one of the 2^32 inputs
+// (NaN in, NaN out): dm_act_check_f32 compares them exhaustively, and
+// tests/test_gpu_act_exact.py runs it.  Sequences that did not survive that
+// check: the reduced argument as fma(x, cc, fma(x, c, -rint(x c))) (3.1M
+// mismatches), siluf's residual written fma(-y, q, x) (x = -0 gives +0).
+// Two more residual steps on either division change nothing.
+// Static totals (hipcc -S; both the short and the _ref copy are in the
+// binary, only the short one runs on in-range data), parent -> now:
+//   kernel                               v_* non-MFMA  v_exp/v_rcp  v_div_*
+//   k_edge_mlp_64x128<2>                 4069 -> 5731   128 -> 256   512
+//   k_gated_mlp_tail_fwd<no keep,fw,base> 4675 -> 6339  128 -> 256   512
+//   k_gated_mlp_tail_bwd<fw>             6473 -> 9923   192 -> 384   768
+//   k_gated_mlp_64<2,keep,out,fw,base>   6644 -> 9219   192 -> 384   768
+//   k_edge_mlp_bwd<true> (none)           342 ->  342     0          0
+// Executed per evaluation: 25 -> 14 (sigf) and 15 (siluf), i.e. per 32-row
+// tile about 700 fewer of 2000 in k_edge_mlp_64x128 and 2700 fewer of 5000
+// in the reverse tail.
+// Measured (tests/perf_act_epilogue.py, 46M rows, median of 5, ms):
+//   form                  _ref    short   returns x (ceiling)
+//   edge_mlp3 no z        12.87   11.49   10.64
+//   tail_fwd fw, base     13.20   11.50    9.60
+//   tail_bwd fw           23.49   19.72   19.40
+//   tail_bwd fw, indexed  21.97   18.77   16.15
+//   mlp3 keep fw, base    27.73   25.53   23.99
+//   mlp3 keep, no out     20.89   20.92   19.43
+//   edge_mlp_bwd (none)    9.01    9.08    9.04
+// Removing the activation arithmetic altogether buys 1.5-5.8 ms per launch,
+// a third to a half of what "MFMA time + VALU issue time, not overlapped"
+// predicts (edge_mlp3: 1600 of 2000 VALU instructions gone for 2.2 ms, the
+// model says 4): VALU issue is partly hidden behind the MFMAs and the
+// memory skeleton, and these kernels are not bound by it alone.
+// Every multiply-add is an explicit fma and contraction is off inside, so the
+// bits do not depend on the calling kernel.
+//   -DDM_ACT_REF         sigf / siluf are the _ref forms (A/B builds)
+//   -DDM_ACT_PROBE_FREE  both return x: WRONG results, timing probes only
+//                        (tests/perf_act_epilogue.py), never shipped
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float sigf_ref(float x) {
+    return 1.0f / (1.0f + expf(-x));
+}
+
+__device__ __forceinline__ float siluf_ref(float x) {
     return x / (1.0f + expf(-x));
+}
+
+constexpr float ACT_FAST_MAX = 87.0f;
+
+// 1 + expf(-x) for |x| <= ACT_FAST_MAX, in libm's operation order
+__device__ __forceinline__ float act_one_plus_exp_neg(float x) {
+#pragma clang fp contract(off)
+    const float c = -0x1.715476p+0f, cc = -0x1.4ae0bep-26f;  // -log2(e), hi + lo
+    const float ph = x * c;
+    const float n = __builtin_rintf(ph);
+    const float pl = __builtin_fmaf(x, cc, __builtin_fmaf(x, c, -ph));
+    const float a = (ph - n) + pl;
+    return 1.0f + __builtin_ldexpf(__builtin_amdgcn_exp2f(a), (int)n);
+}
+
+// true if all N values of every active lane lie in the short sequences'
+// range: one v_cmp per value, the rest is scalar
+template <int N>
+__device__ __forceinline__ bool act_wave_in_range(const float (&x)[N]) {
+#if defined(DM_ACT_PROBE_FREE) || defined(DM_ACT_REF)
+    return true;                     // one form only: nothing to choose
+#else
+    bool outside = false;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        outside |= !(__builtin_fabsf(x[i]) <= ACT_FAST_MAX);
+    return __builtin_amdgcn_ballot_w64(outside) == 0;
+#endif
+}
+
+__device__ __forceinline__ float sigf_fast(float x) {
+    const float y = act_one_plus_exp_neg(x);
+    const float r = __builtin_amdgcn_rcpf(y);
+    return __builtin_fmaf(__builtin_fmaf(-y, r, 1.0f), r, r);
+}
+
+__device__ __forceinline__ float siluf_fast(float x) {
+#pragma clang fp contract(off)
+    const float y = act_one_plus_exp_neg(x);
+    const float r = __builtin_amdgcn_rcpf(y);
+    const float q = x * r;
+    // y q - x, negated in the last fma: keeps the sign of a zero x
+    return __builtin_fmaf(-__builtin_fmaf(y, q, -x), r, q);
+}
+
+// y[i] = sigmoid(x[i]) / SiLU(x[i]) by the short sequence (FAST, valid only
+// where act_wave_in_range held for x) or the _ref form
+template <bool FAST, int N>
+__device__ __forceinline__ void sigf_sel(const float (&x)[N], float (&y)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#if defined(DM_ACT_PROBE_FREE)
+        y[i] = x[i];
+#elif defined(DM_ACT_REF)
+        y[i] = sigf_ref(x[i]);
+#else
+        y[i] = FAST ? sigf_fast(x[i]) : sigf_ref(x[i]);
+#endif
+    }
+}
+
+template <bool FAST, int N>
+__device__ __forceinline__ void siluf_sel(const float (&x)[N], float (&y)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#if defined(DM_ACT_PROBE_FREE)
+        y[i] = x[i];
+#elif defined(DM_ACT_REF)
+        y[i] = siluf_ref(x[i]);
+#else
+        y[i] = FAST ? siluf_fast(x[i]) : siluf_ref(x[i]);
+#endif
+    }
+}
+
+// The same for the N values a lane handles together (a row's columns, a
+// float4): one range test and one branch for all of them
+template <int N>
+__device__ __forceinline__ void sigf_n(const float (&x)[N], float (&y)[N]) {
+    if (__builtin_expect(act_wave_in_range(x), 1))
+        sigf_sel<true>(x, y);
+    else
+        sigf_sel<false>(x, y);
+}
+
+template <int N>
+__device__ __forceinline__ void siluf_n(const float (&x)[N], float (&y)[N]) {
+    if (__builtin_expect(act_wave_in_range(x), 1))
+        siluf_sel<true>(x, y);
+    else
+        siluf_sel<false>(x, y);
+}
+
+__device__ __forceinline__ float sigf(float x) {
+    const float v[1] = {x};
+    float y[1];
+    sigf_n(v, y);
+    return y[0];
+}
+
+__device__ __forceinline__ float siluf(float x) {
+    const float v[1] = {x};
+    float y[1];
+    siluf_n(v, y);
+    return y[0];
+}
+
+__device__ __forceinline__ float4 siluf4(float4 z) {
+    const float v[4] = {z.x, z.y, z.z, z.w};
+    float y[4];
+    siluf_n(v, y);
+    return make_float4(y[0], y[1], y[2], y[3]);
+}
+
+// true if a and b differ as results: other bits, and not both NaN
+__device__ __forceinline__ bool act_differs(float a, float b) {
+    return __float_as_uint(a) != __float_as_uint(b) && !(a != a && b != b);
+}
+
+// Compares sigf (WHICH 0) or siluf (1) with its _ref form on the bit patterns
+// first_bits + [0, count).  Consecutive patterns sit in consecutive lanes, so
+// the waves that straddle +-ACT_FAST_MAX take the _ref branch as a whole;
+// the short sequence is therefore also compared directly wherever it is
+// meant to hold.  Each block stores its own count; the lowest bad pattern is
+// kept with atomicMin.
+template <int WHICH>
+__global__ __launch_bounds__(BLOCK)
+void k_act_check(uint32_t first_bits, uint64_t count,
+                 uint32_t* __restrict__ bad_per_block,
+                 uint32_t* __restrict__ first_bad_bits) {
+    uint32_t bad = 0, lowest = 0xffffffffu;
+    for (uint64_t i = blockIdx.x * (uint64_t)BLOCK + threadIdx.x; i < count;
+         i += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t bits = first_bits + (uint32_t)i;
+        const float x = __uint_as_float(bits);
+        const float want = WHICH ? siluf_ref(x) : sigf_ref(x);
+        bool differs = act_differs(WHICH ? siluf(x) : sigf(x), want);
+        if (__builtin_fabsf(x) <= ACT_FAST_MAX)
+            differs |= act_differs(WHICH ? siluf_fast(x) : sigf_fast(x), want);
+        if (differs) {
+            ++bad;
+            lowest = bits < lowest ? bits : lowest;
+        }
+    }
+    __shared__ uint32_t sbad[BLOCK];
+    sbad[threadIdx.x] = bad;
+    __syncthreads();
+    for (int st = BLOCK / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) sbad[threadIdx.x] += sbad[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) bad_per_block[blockIdx.x] = sbad[0];
+    if (bad) atomicMin(first_bad_bits, lowest);
+}
+
+// out = sigmoid(x) (WHICH 0) or SiLU(x) (1); IMPL 0 the _ref form, 1 the
+// form the kernels use
+template <int WHICH, int IMPL>
+__global__ void k_act_eval(const float* __restrict__ x, int64_t n,
+                           float* __restrict__ out) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const float v = x[t];
+        out[t] = WHICH ? (IMPL ? siluf(v) : siluf_ref(v))
+                       : (IMPL ? sigf(v) : sigf_ref(v));
+    }
 }
 
 __global__ void k_gather_add3_v4(const float4* __restrict__ zs,
@@ -93,8 +324,7 @@ __global__ void k_gather_add3_v4(const float4* __restrict__ zs,
                                      a.z + b.z + e.z, a.w + b.w + e.w);
         out[t] = z;
         if (out_act)
-            out_act[t] = make_float4(siluf(z.x), siluf(z.y), siluf(z.z),
-                                     siluf(z.w));
+            out_act[t] = siluf4(z);
     }
 }
 
@@ -106,7 +336,7 @@ __global__ void k_silu_bwd(const float* __restrict__ go_h,
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
          t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const float zv = z[t];
-        const float s = 1.0f / (1.0f + expf(-zv));
+        const float s = sigf(zv);
         float g = go_h[t] * (s * (1.0f + zv * (1.0f - s)));
         if (go_z) g += go_z[t];
         dz[t] = g;
@@ -135,8 +365,7 @@ __global__ void k_gather_add4_v4(const float4* __restrict__ z1,
                                      a.z + b.z + e.z + v.z, a.w + b.w + e.w + v.w);
         out[t] = z;
         if (out_act)
-            out_act[t] = make_float4(siluf(z.x), siluf(z.y), siluf(z.z),
-                                     siluf(z.w));
+            out_act[t] = siluf4(z);
     }
 }
 
@@ -171,8 +400,9 @@ __global__ void k_gather_add4_v4(const float4* __restrict__ z1,
 //    owning lanes by ds_bpermute.
 //  * Tails: loads of rows >= E are clamped to row E-1, stores predicated.
 // Resources (hipcc -O3, gfx950, kernel-resource-usage remarks):
-//   <2>: 157 VGPR, 0 AGPR, 74 SGPR, 32 KB LDS, 3 waves/SIMD, no scratch
-//   <3>: 143 VGPR, 0 AGPR, 78 SGPR, 32 KB LDS, 3 waves/SIMD, no scratch
+//   <2>: 162 VGPR, 0 AGPR, 80 SGPR, 32 KB LDS, 3 waves/SIMD, no scratch
+//   <3>: 150 VGPR, 0 AGPR, 84 SGPR, 32 KB LDS, 3 waves/SIMD, no scratch
+// (157 / 143 VGPR before the short SiLU and its range test.)
 // Measured at si1m (rocprofv3 kernel trace): <2> at E = 46M rows, 48
 // launches, 14.1 ms average (13.6-16.3) against 42.83 ms (41.7-43.6) for
 // the VALU kernel; <3> at L = 12M rows, 30 launches, 4.42 ms (the VALU
@@ -270,8 +500,10 @@ __device__ __forceinline__ void edge_mlp_epilogue(
                 // 256 B plane stores cost more than the saved copies —
                 // profiles r21 vs r23)
                 float* hp = out_act + row * 128 + c;
+                float hv[4];
+                siluf_n(z, hv);
 #pragma unroll
-                for (int cb = 0; cb < 4; ++cb) hp[32 * cb] = siluf(z[cb]);
+                for (int cb = 0; cb < 4; ++cb) hp[32 * cb] = hv[cb];
             }
             __builtin_amdgcn_sched_barrier(0);   // one row's SiLU at a time
         }
@@ -646,10 +878,6 @@ __global__ void k_rbf_env_bwd(const float* __restrict__ go_exp,
     }
 }
 
-__device__ __forceinline__ float sigf(float x) {
-    return 1.0f / (1.0f + expf(-x));
-}
-
 // out = base + silu(c) * sigmoid(g) * w   (gated-MLP epilogue, fused)
 __global__ void k_gated_combine_fwd(const float* __restrict__ c,
                                     const float* __restrict__ g,
@@ -659,7 +887,10 @@ __global__ void k_gated_combine_fwd(const float* __restrict__ c,
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
          t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const float cv = c[t];
-        float r = cv * sigf(cv) * sigf(g[t]);
+        const float cg[2] = {cv, g[t]};
+        float sg[2];
+        sigf_n(cg, sg);
+        float r = cv * sg[0] * sg[1];
         if (w) r *= w[t];
         if (base) r += base[t];
         out[t] = r;
@@ -677,7 +908,10 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
          t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const float gov = go[t];
         const float cv = c[t], gv = g[t];
-        const float sc = sigf(cv), sg = sigf(gv);
+        const float cg[2] = {cv, gv};
+        float scg[2];
+        sigf_n(cg, scg);
+        const float sc = scg[0], sg = scg[1];
         const float silu_c = cv * sc;
         const float wv = w ? w[t] : 1.0f;
         // d silu(c)/dc = sigmoid(c) * (1 + c * (1 - sigmoid(c)))
@@ -712,7 +946,8 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 //    once all 8 slices are done), and stores its dw slice from there.  MFMA
 //    step 4i+t contracts k = 8i+4h+t; accumulators 0,1 take dc as A and
 //    2,3 take dg.  The slices are loaded and consumed TAIL_CHUNK at a time
-//    so that at most 4*4*TAIL_CHUNK registers of inputs are live.
+//    (2 at a time in the factored-w form) so that at most 4*4*TAIL_CHUNK
+//    registers of inputs are live; the sigmoids' range test is per batch.
 //  * Epilogue in the accumulator layout (col = lane&31, row = (reg&3) +
 //    8*(reg>>2) + 4*(lane>>5)): z is loaded 8 rows at a time (all loads of
 //    a batch in flight before any is used), dz = acc * silu'(z) stored.
@@ -787,10 +1022,12 @@ __device__ __forceinline__ void mlp_tail_epilogue(
             const int64_t row = base + rl;
             if (FULL || row < E) {
                 float* dp = dz + row * 128 + c;
+                float s4[4];
+                sigf_n(zv[t], s4);
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
                     const float x = zv[t][cb];
-                    const float s = 1.0f / (1.0f + expf(-x));
+                    const float s = s4[cb];
                     dp[32 * cb] = acc[cb][r] * (s * (1.0f + x * (1.0f - s)));
                 }
             }
@@ -860,12 +1097,13 @@ __device__ __forceinline__ void mlp_tail_a_phase(
         float (&dcv)[32], float (&dgv)[32],
         const float4* __restrict__ wl9, const float (&bx)[N_RBF], float m,
         float (&dbp)[N_RBF]) {
+    constexpr int CH = HAS_W == 2 ? 2 : TAIL_CHUNK;
 #pragma unroll
-    for (int i0 = 0; i0 < 8; i0 += TAIL_CHUNK) {
-        float4 vgo[TAIL_CHUNK], vc[TAIL_CHUNK], vg[TAIL_CHUNK],
-            vw[TAIL_CHUNK];
+    for (int i0 = 0; i0 < 8; i0 += CH) {
+        float4 vgo[CH], vc[CH], vg[CH],
+            vw[CH];
 #pragma unroll
-        for (int j = 0; j < TAIL_CHUNK; ++j) {
+        for (int j = 0; j < CH; ++j) {
             const int64_t o = off + 8 * (i0 + j);
             vgo[j] = *(const float4*)(go + goff + 8 * (i0 + j));
             vc[j] = *(const float4*)(cp + o);
@@ -873,8 +1111,20 @@ __device__ __forceinline__ void mlp_tail_a_phase(
             if (HAS_W == 1) vw[j] = *(const float4*)(wp + o);
         }
         __builtin_amdgcn_sched_barrier(0);   // the batch in flight first
+        // one range test per batch and the slice loop in two copies: a test
+        // per slice splits the batch into blocks the compiler schedules one
+        // by one, and the HAS_W forms then spill
+        float cg[8 * CH];
 #pragma unroll
-        for (int j = 0; j < TAIL_CHUNK; ++j) {
+        for (int j = 0; j < CH; ++j) {
+            cg[8 * j + 0] = vc[j].x; cg[8 * j + 1] = vc[j].y;
+            cg[8 * j + 2] = vc[j].z; cg[8 * j + 3] = vc[j].w;
+            cg[8 * j + 4] = vg[j].x; cg[8 * j + 5] = vg[j].y;
+            cg[8 * j + 6] = vg[j].z; cg[8 * j + 7] = vg[j].w;
+        }
+        auto slices = [&](auto fast) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
             const float gov4[4] = {vgo[j].x, vgo[j].y, vgo[j].z, vgo[j].w};
             const float cv4[4] = {vc[j].x, vc[j].y, vc[j].z, vc[j].w};
             const float gv4[4] = {vg[j].x, vg[j].y, vg[j].z, vg[j].w};
@@ -884,11 +1134,8 @@ __device__ __forceinline__ void mlp_tail_a_phase(
                 wv4[2] = vw[j].z; wv4[3] = vw[j].w;
             }
             float dwv[4], sc4[4], sg4[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                sc4[t] = sigf(cv4[t]);
-                sg4[t] = sigf(gv4[t]);
-            }
+            sigf_sel<decltype(fast)::value>(cv4, sc4);
+            sigf_sel<decltype(fast)::value>(gv4, sg4);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 float wc[N_RBF];
@@ -918,6 +1165,11 @@ __device__ __forceinline__ void mlp_tail_a_phase(
                     make_float4(dwv[0], dwv[1], dwv[2], dwv[3]);
             __builtin_amdgcn_sched_barrier(0);   // one slice at a time
         }
+        };
+        if (__builtin_expect(act_wave_in_range(cg), 1))
+            slices(std::true_type{});
+        else
+            slices(std::false_type{});
     }
 }
 
@@ -925,7 +1177,9 @@ __device__ __forceinline__ void mlp_tail_a_phase(
 // registers than the dense one (bexp row, mask, dbexp partials, a W row) next
 // to the 64 of dc|dg: within the 168 registers of three waves per SIMD the
 // compiler spills 47 of them (188 B of scratch per lane, with load batches of
-// 1, 2 or 4 slices alike), at two it takes 242 and none.  2 is the build;
+// 1, 2 or 4 slices alike), at two it takes 218 and none with the load batches
+// of 2 slices the A phase uses for this form (242 with batches of 4 and the
+// plain sigmoid; batches of 4 with the range test spill 68 B).  2 is the build;
 // -DDM_FW_BWD_WAVES=3 builds the spilling form for comparison
 // (tests/perf_factored_w.py, profiles/factored_w_standalone.json).
 #ifndef DM_FW_BWD_WAVES
@@ -1360,6 +1614,9 @@ __device__ __forceinline__ void mlp_tail_fwd_rows(
                 cout[o] = cv[0]; cout[o + 32] = cv[1];
                 gout[o] = gv[0]; gout[o + 32] = gv[1];
             }
+            const float cg4[4] = {cv[0], cv[1], gv[0], gv[1]};
+            float s4[4];
+            if (OUT) sigf_n(cg4, s4);
 #pragma unroll
             for (int q = 0; OUT && q < 2; ++q) {
                 // k_gated_combine_fwd rounds each product and the
@@ -1368,7 +1625,7 @@ __device__ __forceinline__ void mlp_tail_fwd_rows(
                 // out equals that kernel's over the same c|g bit for
                 // bit
 #pragma clang fp contract(off)
-                float x = cv[q] * sigf(cv[q]) * sigf(gv[q]);
+                float x = cv[q] * s4[q] * s4[2 + q];
                 if (HAS_W) x *= wq[q];
                 if (HAS_BASE) x += bv[t][q];
                 out[o + 32 * q] = x;
@@ -1615,7 +1872,7 @@ __device__ __forceinline__ void gated_mlp_slice_epilogue(
     }
     if (KEEP && store)
         zrow[16 * HALF + 2 * s] = make_float4(z[0], z[1], z[2], z[3]);
-    hs[s] = make_float4(siluf(z[0]), siluf(z[1]), siluf(z[2]), siluf(z[3]));
+    hs[s] = siluf4(make_float4(z[0], z[1], z[2], z[3]));
 }
 
 // One slice's epilogue shares a scheduling region with 8 MFMAs of the run
@@ -2956,6 +3213,50 @@ int dm_silu_bwd_f32(const float* go_h, const float* go_z, const float* z,
     hipStream_t s = (hipStream_t)stream;
     k_silu_bwd<<<nblocks(total, BLOCK), BLOCK, 0, s>>>(go_h, go_z, z, dz,
                                                        total);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_act_check_f32(int32_t which, uint32_t first_bits, uint64_t count,
+                     uint32_t* bad_per_block, uint32_t* first_bad_bits,
+                     uint64_t stream) {
+    if ((which != 0 && which != 1) || !bad_per_block || !first_bad_bits ||
+        count > (1ull << 32)) {
+        g_err = "dm_act_check_f32: which must be 0 (sigmoid) or 1 (SiLU), "
+                "count <= 2^32, outputs not NULL";
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(first_bad_bits, 0xff, sizeof(uint32_t), s);
+    if (e != hipSuccess) {
+        g_err = hipGetErrorString(e);
+        return (int)e;
+    }
+    if (which == 0)
+        k_act_check<0><<<DM_ACT_CHECK_BLOCKS, BLOCK, 0, s>>>(
+            first_bits, count, bad_per_block, first_bad_bits);
+    else
+        k_act_check<1><<<DM_ACT_CHECK_BLOCKS, BLOCK, 0, s>>>(
+            first_bits, count, bad_per_block, first_bad_bits);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_act_eval_f32(int32_t which, int32_t impl, const float* x, int64_t n,
+                    float* out, uint64_t stream) {
+    if ((which != 0 && which != 1) || (impl != 0 && impl != 1)) {
+        g_err = "dm_act_eval_f32: which and impl must be 0 or 1";
+        return -1;
+    }
+    if (n <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = nblocks(n, BLOCK);
+    switch (which * 2 + impl) {
+    case 0: k_act_eval<0, 0><<<nb, BLOCK, 0, s>>>(x, n, out); break;
+    case 1: k_act_eval<0, 1><<<nb, BLOCK, 0, s>>>(x, n, out); break;
+    case 2: k_act_eval<1, 0><<<nb, BLOCK, 0, s>>>(x, n, out); break;
+    default: k_act_eval<1, 1><<<nb, BLOCK, 0, s>>>(x, n, out); break;
+    }
     DM_CHECK_LAUNCH();
     return 0;
 }

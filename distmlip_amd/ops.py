@@ -175,6 +175,14 @@ def hip_lib() -> ctypes.CDLL:
                                          c_int32, c_uint64]
         lib.dm_zero_rows_f32.restype = c_int32
         lib.dm_zero_rows_f32.argtypes = [fp, lp, c_int64, c_int64, c_uint64]
+        # exact sigmoid / SiLU: check against the plain expressions, evaluate
+        up = POINTER(ctypes.c_uint32)
+        lib.dm_act_check_f32.restype = c_int32
+        lib.dm_act_check_f32.argtypes = [c_int32, ctypes.c_uint32, c_uint64,
+                                         up, up, c_uint64]
+        lib.dm_act_eval_f32.restype = c_int32
+        lib.dm_act_eval_f32.argtypes = [c_int32, c_int32, fp, c_int64, fp,
+                                        c_uint64]
         lib.dm_hip_last_error.restype = c_char_p
         _hip_lib = lib
     return _hip_lib
@@ -306,6 +314,36 @@ def raw_silu_bwd(go_h, go_z, z):
         _fp(go_h), _fp(go_z) if go_z is not None else None, _fp(z), _fp(dz),
         z.numel(), _stream()), "dm_silu_bwd_f32")
     return dz
+
+
+ACT_CHECK_BLOCKS = 4096     # DM_ACT_CHECK_BLOCKS of distmlip_hip.h
+ACT_SIGMOID, ACT_SILU = 0, 1
+
+
+def raw_act_check(which: int, first_bits: int, count: int, device="cuda"):
+    """Compares the kernels' sigmoid (which 0) or SiLU (1) with the plain
+    expression 1/(1+expf(-x)) or x/(1+expf(-x)) on the count <= 2^32 fp32
+    bit patterns from first_bits on.  Returns (mismatches, lowest mismatching
+    pattern or None)."""
+    bad = torch.empty(ACT_CHECK_BLOCKS, dtype=torch.int32, device=device)
+    first = torch.empty(1, dtype=torch.int32, device=device)
+    up = POINTER(ctypes.c_uint32)
+    _check(hip_lib().dm_act_check_f32(
+        which, first_bits, count, ctypes.cast(bad.data_ptr(), up),
+        ctypes.cast(first.data_ptr(), up), _stream()), "dm_act_check_f32")
+    n = int(bad.to(torch.int64).sum().item())
+    return n, (first.item() & 0xffffffff) if n else None
+
+
+def raw_act_eval(which: int, x: torch.Tensor, ref: bool) -> torch.Tensor:
+    """sigmoid (which 0) or SiLU (1) of every element of x: the plain
+    expression (ref) or the function the kernels call."""
+    _chk_f32(x)
+    out = torch.empty_like(x)
+    _check(hip_lib().dm_act_eval_f32(
+        which, 0 if ref else 1, _fp(x), x.numel(), _fp(out), _stream()),
+        "dm_act_eval_f32")
+    return out
 
 
 class _GatherAdd3(torch.autograd.Function):

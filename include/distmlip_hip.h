@@ -53,6 +53,28 @@ int dm_gather_add4_f32(const float* z1, const float* z2, const float* za,
 int dm_silu_bwd_f32(const float* go_h, const float* go_z, const float* z,
                     float* dz, int64_t total, uint64_t stream);
 
+/* The CHGNet kernels evaluate sigmoid(x) = 1/(1 + expf(-x)) and
+ * SiLU(x) = x/(1 + expf(-x)) through one pair of device functions, a shorter
+ * instruction sequence that returns the bits of those expressions for every
+ * fp32 input.  The two entries below expose the pair for checking.
+ * which: 0 sigmoid, 1 SiLU.
+ *
+ * dm_act_check_f32 compares the kernels' function with the plain expression
+ * on the count (<= 2^32) bit patterns first_bits, first_bits + 1, ...
+ * (wrapping).  Two NaNs count as equal.  bad_per_block
+ * [DM_ACT_CHECK_BLOCKS] receives one mismatch count per block (sum them);
+ * *first_bad_bits receives the lowest mismatching pattern, or 0xffffffff
+ * (a NaN, which cannot mismatch) if there is none.
+ *
+ * dm_act_eval_f32: out[i] = f(x[i]) for i < n, with impl 0 the plain
+ * expression and impl 1 the kernels' function. */
+#define DM_ACT_CHECK_BLOCKS 4096
+int dm_act_check_f32(int32_t which, uint32_t first_bits, uint64_t count,
+                     uint32_t* bad_per_block, uint32_t* first_bad_bits,
+                     uint64_t stream);
+int dm_act_eval_f32(int32_t which, int32_t impl, const float* x, int64_t n,
+                    float* out, uint64_t stream);
+
 /* out[n, :] = (base ? base[n, :] : 0) + sum_{j in [row_ptr[n], row_ptr[n+1])}
  *             msg[j, :]
  * msg is DST-SORTED (builder layout).  THE judged scatter-add kernel. */
