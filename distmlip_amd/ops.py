@@ -108,6 +108,14 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_rot_dD_f32.restype = c_int32
         lib.dm_rot_dD_f32.argtypes = [fp, fp, ip, c_int32, fp, c_int64,
                                       c_int32, c_uint64]
+        # SO(2) convolution on bf16 MFMA (csrc/so2.hip)
+        hp = POINTER(ctypes.c_uint16)
+        lib.dm_so2_conv_fwd_bf16.restype = c_int32
+        lib.dm_so2_conv_fwd_bf16.argtypes = [fp, fp, fp, hp, fp, c_int64,
+                                             c_int32, c_uint64]
+        lib.dm_so2_conv_bwd_bf16.restype = c_int32
+        lib.dm_so2_conv_bwd_bf16.argtypes = [fp, fp, fp, fp, hp, fp, fp, fp,
+                                             c_int64, c_int32, c_uint64]
         lib.dm_mace_symc_fwd_f32.restype = c_int32
         lib.dm_mace_symc_fwd_f32.argtypes = [fp, ip, fp, ip, fp, c_int32,
                                              fp, c_int64, c_int32, c_int32,
@@ -194,6 +202,11 @@ def _fp(t):
 
 def _ip(t):
     return ctypes.cast(t.data_ptr(), POINTER(c_int32))
+
+
+def _hp(t):
+    """16-bit words (a bf16 tensor's storage)."""
+    return ctypes.cast(t.data_ptr(), POINTER(ctypes.c_uint16))
 
 
 def _stream():

@@ -175,14 +175,18 @@ def _rot_dD_raw(go_e, h, idx, trans):
 
 
 class _RotGather(torch.autograd.Function):
-    """out[e] = D_e . h[idx[e]]   (h [N,9,C] f32, D [E,9,9] f32)."""
+    """out[e] = D_e . h[idx[e]]   (h [N,9,C] f32, D [E,9,9] f32).
+    ordered: sum dh in a fixed order (sorted index_put) instead of with
+    atomic adds.  The bf16 mode rounds what follows to bf16, which turns the
+    last-bit noise of atomics into ~2e-3 of the force scale run to run."""
 
     @staticmethod
-    def forward(ctx, h, D, idx):
+    def forward(ctx, h, D, idx, ordered=False):
         h = h.contiguous()
         D = D.contiguous()
         out = _rot_gather_raw(h, idx, D.view(-1, 81), 0)
         ctx.save_for_backward(h, D, idx)
+        ctx.ordered = ordered
         return out
 
     @staticmethod
@@ -191,9 +195,13 @@ class _RotGather(torch.autograd.Function):
         go = go.contiguous()
         # dh: scatter of D^T . go to the gathered rows
         tmp = _rot_gather_raw(go, None, D.view(-1, 81), 1)
-        dh = torch.zeros_like(h).index_add_(0, idx.long(), tmp)
+        if ctx.ordered:
+            dh = torch.zeros_like(h).index_put_((idx.long(),), tmp,
+                                                accumulate=True)
+        else:
+            dh = torch.zeros_like(h).index_add_(0, idx.long(), tmp)
         dD = _rot_dD_raw(go, h, idx, 0)
-        return dh, dD, None
+        return dh, dD, None, None
 
 
 class _RotScatter(torch.autograd.Function):
@@ -279,6 +287,115 @@ def so2_conv_split(conv: SO2Conv, xs: torch.Tensor, xd: torch.Tensor,
         out[:, plus, :] = op.view(E, len(plus), C) * g
         out[:, minus, :] = om.view(E, len(plus), C) * g
     return out
+
+
+# ---------------------------------------------------------------------------
+# fused SO(2) convolution on bf16 MFMA (csrc/so2.hip): dm_so2_conv_{fwd,bwd}
+# _bf16 replace the split-GEMM composition above in the bf16 engine mode
+# ---------------------------------------------------------------------------
+
+def _frag_pack(mats):
+    """[K, N] matrices (one, or the (r, i) pair of an m > 0 group) -> the
+    B-fragment order of v_mfma_f32_32x32x16_bf16,
+    [kstep][r|i][ntile][lane][8] with lane = 32 (k // 8 % 2) + n % 32."""
+    out = []
+    for B in mats:
+        K, N = B.shape
+        v = B.reshape(K // 16, 2, 8, N // 32, 32)      # ks, g, e, nt, c
+        out.append(v.permute(0, 3, 1, 4, 2))           # ks, nt, g, c, e
+    return torch.stack(out, dim=1).reshape(-1)
+
+
+def _so2_pack(conv: SO2Conv):
+    """bf16 weight images of the fused kernels, cached on the frozen module:
+    (forward, transposed-per-side) flat bf16 tensors of 38 C^2 elements."""
+    key = tuple(p._version for p in conv.parameters()) \
+        + (str(conv.w0.device),)
+    cached = getattr(conv, "_dm_pack", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    lmax = conv.lmax
+    assert lmax == 2
+    C = conv.w0.shape[0] // (lmax + 1)
+    with torch.no_grad():
+        groups = [(conv.w0.float(),)] + [
+            (conv.wr[m - 1].float(), conv.wi[m - 1].float())
+            for m in range(1, lmax + 1)]
+        # forward: B = W^T, [K = (row, side, c), N = (row, c)]
+        fwd = torch.cat([_frag_pack([w.t() for w in g]) for g in groups])
+        # reverse, per side: B = W[:, side columns] ([K = out, N = in]),
+        # and -Wi: u_p = g_p Wr + g_m Wi, u_m = -g_p Wi + g_m Wr
+        bwd = []
+        for side in (0, 1):
+            for m, g in enumerate(groups):
+                nl = lmax + 1 - m
+                cols = [w.view(w.shape[0], nl, 2, C)[:, :, side, :]
+                        .reshape(w.shape[0], nl * C) for w in g]
+                if m > 0:
+                    cols[1] = -cols[1]
+                bwd.append(_frag_pack(cols))
+        packs = (fwd.bfloat16().contiguous(),
+                 torch.cat(bwd).bfloat16().contiguous())
+    if not any(p.requires_grad for p in conv.parameters()):
+        conv._dm_pack = (key, packs)
+    return packs
+
+
+class _So2ConvFused(torch.autograd.Function):
+    """mt = so2_conv(conv, xs || xd, gate) with bf16 operands and fp32
+    accumulation; backward is one launch (dxs, dxd, dgate), the weights
+    are frozen."""
+
+    @staticmethod
+    def forward(ctx, xs, xd, gate, wf, wt):
+        from distmlip_amd.ops import (_check, _chk_f32, _fp, _hp, _stream,
+                                      hip_lib)
+        xs, xd, gate = xs.contiguous(), xd.contiguous(), gate.contiguous()
+        _chk_f32(xs, xd, gate)
+        E, S, C = xs.shape
+        assert S == 9 and xd.shape == xs.shape and gate.shape == (E, 3)
+        assert wf.numel() == 38 * C * C and wt.numel() == 38 * C * C
+        mt = torch.empty_like(xs)
+        _check(hip_lib().dm_so2_conv_fwd_bf16(
+            _fp(xs), _fp(xd), _fp(gate), _hp(wf), _fp(mt), E, C, _stream()),
+            "dm_so2_conv_fwd_bf16")
+        ctx.save_for_backward(xs, xd, gate, wt)
+        return mt
+
+    @staticmethod
+    def backward(ctx, go):
+        from distmlip_amd.ops import (_check, _chk_f32, _fp, _hp, _stream,
+                                      hip_lib)
+        xs, xd, gate, wt = ctx.saved_tensors
+        go = go.contiguous()
+        _chk_f32(go)
+        E, _, C = xs.shape
+        dxs = torch.empty_like(xs)
+        dxd = torch.empty_like(xd)
+        dg2 = torch.empty(2, E, 3, dtype=xs.dtype, device=xs.device)
+        _check(hip_lib().dm_so2_conv_bwd_bf16(
+            _fp(go), _fp(xs), _fp(xd), _fp(gate), _hp(wt), _fp(dxs),
+            _fp(dxd), _fp(dg2), E, C, _stream()), "dm_so2_conv_bwd_bf16")
+        return dxs, dxd, dg2[0] + dg2[1], None, None
+
+
+def so2_conv_fused(conv: SO2Conv, xs: torch.Tensor, xd: torch.Tensor,
+                   gate: torch.Tensor) -> torch.Tensor:
+    """so2_conv over separate rotated src/dst tensors [E,9,C] in one HIP
+    kernel: bf16-rounded operands, fp32 accumulation, fp32 gate; returns
+    fp32 [E,9,C].  Frozen weights only (see so2_kernel_available)."""
+    if any(p.requires_grad for p in conv.parameters()):
+        raise RuntimeError("so2_conv_fused: the conv weights must be frozen")
+    wf, wt = _so2_pack(conv)
+    return _So2ConvFused.apply(xs.float(), xd.float(), gate.float(), wf, wt)
+
+
+def so2_kernel_available(conv: SO2Conv, x_like: torch.Tensor) -> bool:
+    import os
+    return (os.environ.get("DM_UMA_SO2", "hip") != "torch"
+            and x_like.is_cuda and conv.lmax == 2
+            and x_like.shape[-1] in (64, 128)
+            and not any(p.requires_grad for p in conv.parameters()))
 
 
 def rot_kernels_available(x_like: torch.Tensor, lmax: int) -> bool:

@@ -267,12 +267,23 @@ class UmaSpmdEngine:
                             def rchunk(hf_, gate_, _n0=n0, _n1=n1,
                                        _e0=e0, _e1=e1, _b=_blk):
                                 Dc = D[_e0:_e1].float()
+                                fused = ac and uma_ops.so2_kernel_available(
+                                    _b.msg, hf_)
+                                # the fused bf16 path sums the gather
+                                # reverse in a fixed order: bf16 mode then
+                                # repeats itself bit for bit
                                 xs = uma_ops._RotGather.apply(
-                                    hf_, Dc, pd.src[_e0:_e1])
+                                    hf_, Dc, pd.src[_e0:_e1], fused)
                                 xd = uma_ops._RotGather.apply(
-                                    hf_, Dc, pd.dst[_e0:_e1])
-                                mt = uma_ops.so2_conv_split(
-                                    _b.msg, xs, xd, gate_[_e0:_e1], C)
+                                    hf_, Dc, pd.dst[_e0:_e1], fused)
+                                if fused:
+                                    # one fused bf16-MFMA kernel
+                                    # (csrc/so2.hip), fp32 accumulation
+                                    mt = uma_ops.so2_conv_fused(
+                                        _b.msg, xs, xd, gate_[_e0:_e1])
+                                else:
+                                    mt = uma_ops.so2_conv_split(
+                                        _b.msg, xs, xd, gate_[_e0:_e1], C)
                                 rp_loc = (pd.row_ptr[_n0:_n1 + 1]
                                           - pd.row_ptr[_n0]).contiguous()
                                 dst_rel = (pd.dst[_e0:_e1].int()

@@ -396,6 +396,26 @@ int dm_rot_dD_f32(const float* go, const float* h, const int32_t* idx,
                   int32_t trans, float* dD, int64_t E, int32_t C,
                   uint64_t stream);
 
+/* eSCN/UMA SO(2) convolution in the edge frame, fused (csrc/so2.hip):
+ * uma_ops.so2_conv over the rotated features xs, xd [E,9,C] fp32 as
+ * dm_rot_gather_f32 writes them, gate [E,3] fp32, lmax 2, C in {64,128}.
+ * Operands are rounded to bf16 (nearest even), products accumulate in fp32
+ * on v_mfma_f32_32x32x16_bf16, the gate is applied in fp32.  wpack /
+ * wpack_t are the bf16 fragment-order weight images of uma_ops._so2_pack
+ * (38 C^2 elements each; forward, and transposed per side for the reverse).
+ *   fwd: mt [E,9,C], every row written once.
+ *   bwd: u = W^T bf16(go); dxs, dxd = gate_m . u; dgate2 [2,E,3] holds per
+ *        side sum u . bf16(x) over the rows of m (the caller adds the two
+ *        sides).  Weights are frozen: no weight gradient.
+ * E == 0 returns without a launch. */
+int dm_so2_conv_fwd_bf16(const float* xs, const float* xd, const float* gate,
+                         const uint16_t* wpack, float* mt, int64_t E,
+                         int32_t C, uint64_t stream);
+int dm_so2_conv_bwd_bf16(const float* go, const float* xs, const float* xd,
+                         const float* gate, const uint16_t* wpack_t,
+                         float* dxs, float* dxd, float* dgate2, int64_t E,
+                         int32_t C, uint64_t stream);
+
 /* TensorNet tensor message pass, fused per node.  Replaces the matgl
  * TensorNetInteraction message step the reference's TensorNet_Dist delegates
  * to (implementations/matgl/models/tensornet.py, the per-layer loop around
