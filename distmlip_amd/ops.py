@@ -116,6 +116,13 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_so2_conv_bwd_bf16.restype = c_int32
         lib.dm_so2_conv_bwd_bf16.argtypes = [fp, fp, fp, fp, hp, fp, fp, fp,
                                              c_int64, c_int32, c_uint64]
+        # S2 grid activation on fp32 MFMA (csrc/s2act.hip)
+        lib.dm_s2_act_fwd_f32.restype = c_int32
+        lib.dm_s2_act_fwd_f32.argtypes = [fp, fp, fp, fp, c_int64, c_int32,
+                                          c_int32, c_uint64]
+        lib.dm_s2_act_bwd_f32.restype = c_int32
+        lib.dm_s2_act_bwd_f32.argtypes = [fp, fp, fp, fp, fp, c_int64,
+                                          c_int32, c_int32, c_uint64]
         lib.dm_mace_symc_fwd_f32.restype = c_int32
         lib.dm_mace_symc_fwd_f32.argtypes = [fp, ip, fp, ip, fp, c_int32,
                                              fp, c_int64, c_int32, c_int32,

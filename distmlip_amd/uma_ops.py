@@ -66,7 +66,14 @@ def s2_act(x: torch.Tensor, cfg: UMAConfig,
     """Pointwise silu on the sphere: to grid, silu, band-limited
     projection back (the eSCN grid activation).  Chunked over nodes —
     the [N, G, C] grid tensor at 238k atoms x 512 points x 128 channels
-    is 62 GB fp32, so it is never materialized whole."""
+    is 62 GB fp32, so it is never materialized whole.  Where
+    s2_kernel_available holds, the whole tensor goes through one fused HIP
+    kernel per pass instead (csrc/s2act.hip; fp32 result), which stores no
+    grid tensor at all; the composition below is the DM_UMA_S2=torch path,
+    the CPU / fp64 path and the reference of the tests."""
+    if s2_kernel_available(x, cfg):
+        to_g, from_g = _grids(cfg, x.new_empty(0, dtype=torch.float32))
+        return _S2ActFused.apply(x.float(), to_g, from_g)
     to_g, from_g = _grids(cfg, x)
 
     def one(t):
@@ -91,6 +98,65 @@ def s2_act(x: torch.Tensor, cfg: UMAConfig,
         else:
             outs.append(one(xc))
     return torch.cat(outs, dim=0)
+
+
+# columns (node x channel) per block of the fused S2 activation kernels
+# (csrc/s2act.hip S2_COLS): 4 waves of two 16-channel blocks
+S2_COLS = 128
+
+
+def s2_n_tile(C: int) -> int:
+    """Nodes one block of the fused S2 activation covers at C channels."""
+    return max(1, S2_COLS // C)
+
+
+class _S2ActFused(torch.autograd.Function):
+    """out = s2_act(x) for x [N, 9, C] fp32 in one HIP kernel (to grid, silu,
+    back; csrc/s2act.hip).  Only x is saved: the backward, one launch,
+    recomputes the grid values.  The grid matrices are constants."""
+
+    @staticmethod
+    def forward(ctx, x, to_g, from_g):
+        from distmlip_amd.ops import _check, _chk_f32, _fp, _stream, hip_lib
+        x, to_g, from_g = x.contiguous(), to_g.contiguous(), from_g.contiguous()
+        _chk_f32(x, to_g, from_g)
+        N, S, C = x.shape
+        G = to_g.shape[0]
+        assert S == 9 and to_g.shape == (G, 9) and from_g.shape == (9, G)
+        out = torch.empty_like(x)
+        _check(hip_lib().dm_s2_act_fwd_f32(
+            _fp(x), _fp(to_g), _fp(from_g), _fp(out), N, C, G, _stream()),
+            "dm_s2_act_fwd_f32")
+        ctx.save_for_backward(x, to_g, from_g)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        from distmlip_amd.ops import _check, _chk_f32, _fp, _stream, hip_lib
+        x, to_g, from_g = ctx.saved_tensors
+        go = go.contiguous()
+        _chk_f32(go)
+        N, _, C = x.shape
+        dx = torch.empty_like(x)
+        _check(hip_lib().dm_s2_act_bwd_f32(
+            _fp(go), _fp(x), _fp(to_g), _fp(from_g), _fp(dx), N, C,
+            to_g.shape[0], _stream()), "dm_s2_act_bwd_f32")
+        return dx, None, None
+
+
+def s2_kernel_available(x: torch.Tensor, cfg: UMAConfig) -> bool:
+    """DM_UMA_S2: unset = the kernel for fp32 input, the torch composition for
+    bf16 input (autocast); "hip" = the kernel for both; "torch" = neither.
+    The bf16 engine mode is not switched by default: through the kernel its
+    chunked-against-unchunked force difference is 0.095 at force scale 44.9,
+    past the 1e-3 bound of test_so2_fused_engine_chunked (0.040 before)."""
+    import os
+    mode = os.environ.get("DM_UMA_S2", "")
+    return (mode != "torch" and x.is_cuda
+            and (x.dtype == torch.float32
+                 or (x.dtype == torch.bfloat16 and mode == "hip"))
+            and cfg.lmax == 2 and x.shape[-1] % 32 == 0
+            and cfg.grid_phi % 32 == 0)     # hence G % 32 == 0
 
 
 def edge_scalars(core: UMACore, lengths: torch.Tensor, spec_src,

@@ -416,6 +416,25 @@ int dm_so2_conv_bwd_bf16(const float* go, const float* xs, const float* xd,
                          float* dxs, float* dxd, float* dgate2, int64_t E,
                          int32_t C, uint64_t stream);
 
+/* eSCN/UMA S2 grid activation, fused (csrc/s2act.hip): uma_ops.s2_act over
+ * x [N,9,C] fp32 (the layout of node_ffn), lmax 2, with the matrices of
+ * uma_model.s2_grid: to_g [G,9], from_g [9,G], fp32.  Operands and
+ * accumulation are fp32 on v_mfma_f32_16x16x4_f32, silu is the exact form
+ * of the gated-MLP kernels; the [N,C,G] grid tensor is never stored.
+ *   fwd: out[n,s,c] = sum_g from_g[s,g] silu(sum_t to_g[g,t] x[n,t,c])
+ *   bwd: f = to_g x (recomputed), q[g] = sum_s from_g[s,g] go[n,s,c],
+ *        dx[n,t,c] = sum_g to_g[g,t] silu'(f) q
+ * The sum over g has a fixed order and no atomics: launches repeat bit for
+ * bit.  C % 32 == 0, G % 32 == 0, pointers 16-byte aligned; anything else
+ * sets the last error and returns non-zero.  N == 0 returns without a
+ * launch. */
+int dm_s2_act_fwd_f32(const float* x, const float* to_g, const float* from_g,
+                      float* out, int64_t N, int32_t C, int32_t G,
+                      uint64_t stream);
+int dm_s2_act_bwd_f32(const float* go, const float* x, const float* to_g,
+                      const float* from_g, float* dx, int64_t N, int32_t C,
+                      int32_t G, uint64_t stream);
+
 /* TensorNet tensor message pass, fused per node.  Replaces the matgl
  * TensorNetInteraction message step the reference's TensorNet_Dist delegates
  * to (implementations/matgl/models/tensornet.py, the per-layer loop around
