@@ -24,7 +24,6 @@ fp summation order.
 """
 from __future__ import annotations
 
-import os
 from copy import deepcopy
 from typing import List, Optional
 
@@ -33,6 +32,8 @@ import torch
 from torch import nn
 
 import distmlip_amd
+from distmlip_amd import mlp_path
+from distmlip_amd.conv import _records, first3, first4
 from distmlip_amd.model import (
     CHGNetConfig,
     CHGNetCore,
@@ -121,101 +122,62 @@ def _second_layer_packed(h, w2, b2, d: int):
     return torch.baddbmm(b2, hb, w2)
 
 
-def _use_fused(rows: int) -> bool:
-    """Fused first-layer kernel policy: on, in no-grad and in
-    grad-recording passes alike.  With the fp32-MFMA kernel the fused side
-    wins the recording-path A/B at li100k (same box, alternating runs,
-    op-by-op path, i.e. DM_WHOLE_GRAPH=0): 127.3 / 127.7 / 127.8 ms/step
-    fused against 137.0 / 137.1 / 137.1 unfused (rocBLAS + gather-add)
-    (profiles/r3_policy_li100k_opbyop_*.json).  The earlier VALU kernel
-    lost that A/B (187 vs 172 ms in run 25; 158 vs 137 re-measured next to
-    the numbers above), which is why recording passes used to stay unfused
-    below 40M rows.  In no-grad passes (checkpoint outer forward,
-    inference) the kernel also skips the z save and the [E,128] GEMM
-    round-trip (~4 GB vs ~9 GB of HBM per MLP), and in recording passes it
-    materializes one fewer [E,128] transient per MLP, which is what
-    decides whether 2M atoms fit in 288 GB.  `rows` is kept for callers
-    and for size-dependent policies.  DM_NO_FUSED_MLP=1 turns the kernel
-    off for A/B runs; DM_FUSED_MLP=1 is accepted and is the default."""
-    return os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
+# Fused first-layer kernel policy (mlp_path.fused_first): on, in no-grad and
+# in grad-recording passes alike.  With the fp32-MFMA kernel the fused side
+# wins the recording-path A/B at li100k (same box, alternating runs,
+# op-by-op path, i.e. DM_WHOLE_GRAPH=0): 127.3 / 127.7 / 127.8 ms/step
+# fused against 137.0 / 137.1 / 137.1 unfused (rocBLAS + gather-add)
+# (profiles/r3_policy_li100k_opbyop_*.json).  In no-grad passes (checkpoint
+# outer forward, inference) the kernel also skips the z save and the [E,128]
+# GEMM round-trip (~4 GB vs ~9 GB of HBM per MLP), and in recording passes it
+# materializes one fewer [E,128] transient per MLP, which is what decides
+# whether 2M atoms fit in 288 GB.
+
+
+def _gated_mlp_tail(ops, zh, tail, packs, d, w, base):
+    """Second layer + combine of one gated MLP after its first layer gave zh:
+    (z, h) with tail, else h.
+
+    tail (ops.mlp_tail: one autograd node whose backward is one kernel from
+    go to dz) is taken when h requires grad, so no-grad passes keep the plain
+    path.  Passes that record nothing take ops.mlp_tail_act (one kernel, no
+    cg transient) where mlp_path allows; recording passes reach the same
+    kernel in its cg-keeping form through ops.mlp_tail.  That includes the
+    outer forward of a non-reentrant checkpoint, which records like any other
+    pass and has its saves dropped by the checkpoint's hooks."""
+    wcg, _, w2, b2 = packs[:4]
+    z, h = zh if tail else (None, zh)
+    if tail and h.requires_grad:
+        return ops.mlp_tail(z, h, w2, b2, w, base)
+    if (not wcg.requires_grad and not _records(h, w, base)
+            and mlp_path.fused_tail_fwd(ops, d, "mlp_tail_act")):
+        return ops.mlp_tail_act(h, w2, b2, w, base)
+    cg = _second_layer_packed(h, w2, b2, d)
+    return ops.gated_combine_packed(cg, w, base)
 
 
 def _use_fused_tail(ops, d: int, wcg) -> bool:
-    """Fused reverse tail policy (ops.mlp_tail: second layer + combine as
-    one autograd node whose backward is one kernel from go to dz): on for
-    d = 64 with frozen weights on a backend that has it.  The caller adds
-    the per-call condition that h requires grad, so no-grad passes keep the
-    plain path.  DM_NO_FUSED_MLP_BWD=1 restores the three-kernel chain
-    (gated_combine_bwd, two GEMMs, silu_bwd) for A/B runs in one build."""
-    return (d == 64 and not wcg.requires_grad and hasattr(ops, "mlp_tail")
-            and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1")
-
-
-def _use_fused_tail_fwd(ops, d: int, wcg, h, w, base) -> bool:
-    """Fused forward tail policy for passes that record nothing
-    (ops.mlp_tail_act: second layer + combine in one kernel, no cg
-    transient): on for d = 64 with frozen weights on a backend that has it,
-    when no input of the tail needs a gradient (energy-only inference, any
-    torch.no_grad pass).  Recording passes reach the same kernel in its
-    cg-keeping form through ops.mlp_tail; that includes the outer forward of
-    a non-reentrant checkpoint, which records like any other pass and has
-    its saves dropped by the checkpoint's hooks.  DM_NO_FUSED_MLP_FWD=1
-    restores baddbmm + dm_gated_combine_fwd_f32 in both, for A/B runs in one
-    build."""
-    if not (d == 64 and not wcg.requires_grad and hasattr(ops, "mlp_tail_act")
-            and os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1"):
-        return False
-    return not (torch.is_grad_enabled() and any(
-        t is not None and t.requires_grad for t in (h, w, base)))
+    return not wcg.requires_grad and mlp_path.fused_tail_bwd(ops, d,
+                                                             "mlp_tail")
 
 
 def gated_mlp_split3(mlp: GatedMLP, v, e, pd, ops, d: int, w=None, base=None):
     """GatedMLP over cat(v[src], v[dst], e) via split-linear + one 2h-wide
     gather_add3, finished by the fused gated-combine epilogue:
     returns base + silu(core2(silu(z_c))) * sigmoid(gate2(silu(z_g))) * w."""
-    wcg, bcg, w2, b2, fusedT = _packed_weights(mlp)
-    ws, wd = wcg[:, :d], wcg[:, d:2 * d]
-    tail = _use_fused_tail(ops, d, wcg)
-    if (d == 64 and not wcg.requires_grad and _use_fused(e.shape[0])
-            and hasattr(ops, "edge_mlp3_act")):
-        # per-edge GEMM fused into the gather kernel (no [E,2d] transient)
-        first = ops.edge_mlp3_zh if tail else ops.edge_mlp3_act
-        zh = first(e, fusedT, bcg, v @ ws.t(), v @ wd.t(), pd)
-    else:
-        we = wcg[:, 2 * d:]
-        first = ops.gather_add3_zh if tail else ops.gather_add3_act
-        zh = first(v @ ws.t(), v @ wd.t(), torch.addmm(bcg, e, we.t()), pd)
-    z, h = zh if tail else (None, zh)
-    if tail and h.requires_grad:
-        return ops.mlp_tail(z, h, w2, b2, w, base)
-    if _use_fused_tail_fwd(ops, d, wcg, h, w, base):
-        return ops.mlp_tail_act(h, w2, b2, w, base)
-    cg = _second_layer_packed(h, w2, b2, d)
-    return ops.gated_combine_packed(cg, w, base)
+    packs = _packed_weights(mlp)
+    tail = _use_fused_tail(ops, d, packs[0])
+    zh = first3(ops, pd, v, e, packs, d, zh=tail)
+    return _gated_mlp_tail(ops, zh, tail, packs, d, w, base)
 
 
 def gated_mlp_split4(mlp: GatedMLP, n, a, v, pd, ops, d: int, w=None,
                      base=None):
     """GatedMLP over cat(n[l_src], n[l_dst], a, v[center]), same structure."""
-    wcg, bcg, w2p, b2p, fusedT = _packed_weights(mlp)
-    w1, w2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
-    tail = _use_fused_tail(ops, d, wcg)
-    if (d == 64 and not wcg.requires_grad and _use_fused(a.shape[0])
-            and hasattr(ops, "edge_mlp4_act")):
-        first = ops.edge_mlp4_zh if tail else ops.edge_mlp4_act
-        zh = first(a, fusedT, bcg, n @ w1.t(), n @ w2.t(), v @ wv.t(), pd)
-    else:
-        wa = wcg[:, 2 * d:3 * d]
-        first = ops.gather_add4_zh if tail else ops.gather_add4_act
-        zh = first(n @ w1.t(), n @ w2.t(), torch.addmm(bcg, a, wa.t()),
-                   v @ wv.t(), pd)
-    z, h = zh if tail else (None, zh)
-    if tail and h.requires_grad:
-        return ops.mlp_tail(z, h, w2p, b2p, w, base)
-    if _use_fused_tail_fwd(ops, d, wcg, h, w, base):
-        return ops.mlp_tail_act(h, w2p, b2p, w, base)
-    cg = _second_layer_packed(h, w2p, b2p, d)
-    return ops.gated_combine_packed(cg, w, base)
+    packs = _packed_weights(mlp)
+    tail = _use_fused_tail(ops, d, packs[0])
+    zh = first4(ops, pd, n, a, v, packs, d, zh=tail)
+    return _gated_mlp_tail(ops, zh, tail, packs, d, w, base)
 
 
 class PartitionData:

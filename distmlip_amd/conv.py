@@ -31,9 +31,9 @@ profiles/row_exchange_*).
 """
 from __future__ import annotations
 
-import os
-
 import torch
+
+from distmlip_amd import mlp_path
 
 
 def _second_fwd(h, w2, b2, d):
@@ -51,38 +51,34 @@ def _second_bwd(dcg, w2, d):
 
 def _mlp_tail_bwd(ops, go, cg, w, z, w2, d):
     """(dz, dw) from the gradient go of r_combine_fwd(cg, w, base): one
-    kernel where the backend has r_mlp_tail_bwd (d = 64), else combine
-    reverse + second-layer GEMMs + silu reverse.  DM_NO_FUSED_MLP_BWD=1
-    forces the latter for A/B runs."""
-    if (d == 64 and hasattr(ops, "r_mlp_tail_bwd")
-            and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1"):
+    kernel where mlp_path allows r_mlp_tail_bwd, else combine reverse +
+    second-layer GEMMs + silu reverse."""
+    if mlp_path.fused_tail_bwd(ops, d):
         return ops.r_mlp_tail_bwd(go, cg, w, z, w2)
     dcg, dw = ops.r_combine_bwd(go, cg, w)
     return ops.r_silu_bwd(_second_bwd(dcg, w2, d), z), dw
 
 
-def _fused_tail_fwd(ops, d, name):
-    return (d == 64 and hasattr(ops, name)
-            and os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1")
-
-
 def _mlp_tail_fwd(ops, h, w2, b2, w, base, d):
     """(cg, out) with cg = the second layer over h and out =
-    r_combine_fwd(cg, w, base): one kernel where the backend has
-    r_mlp_tail_fwd (d = 64), else baddbmm + combine.  DM_NO_FUSED_MLP_FWD=1
-    forces the latter for A/B runs."""
-    if _fused_tail_fwd(ops, d, "r_mlp_tail_fwd"):
+    r_combine_fwd(cg, w, base): one kernel where mlp_path allows
+    r_mlp_tail_fwd, else baddbmm + combine."""
+    if mlp_path.fused_tail_fwd(ops, d):
         return ops.r_mlp_tail_fwd(h, w2, b2, w, base)
     cg = _second_fwd(h, w2, b2, d)
     return cg, ops.r_combine_fwd(cg, w, base)
 
 
+def _records(*ts):
+    return torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in ts)
+
+
 def _mlp_tail_act(ops, h, w2, b2, w, base, d):
     """out of _mlp_tail_fwd alone, for the save-nothing forwards: no cg is
-    written where the backend has mlp_tail_act."""
-    records = torch.is_grad_enabled() and any(
-        t is not None and t.requires_grad for t in (h, w, base))
-    if not records and _fused_tail_fwd(ops, d, "mlp_tail_act"):
+    written where mlp_path allows mlp_tail_act."""
+    if (not _records(h, w, base)
+            and mlp_path.fused_tail_fwd(ops, d, "mlp_tail_act")):
         return ops.mlp_tail_act(h, w2, b2, w, base)
     return ops.gated_combine_packed(_second_fwd(h, w2, b2, d), w, base)
 
@@ -92,66 +88,70 @@ def _unpack_edge(packs, d):
     return wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:], bcg, w2, b2
 
 
+def _unpack_line(packs, d):
+    wcg, bcg, w2, b2 = packs[:4]
+    return (wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:3 * d], wcg[:, 3 * d:],
+            bcg, w2, b2)
+
+
 def _fusedT(packs):
     """The [d,2d] fusedT pack of a 5-element pack, None for a 4-pack."""
     return packs[4] if len(packs) > 4 else None
 
 
-def _fused_first(ops, packs, d):
-    """fusedT when the first layer can run as r_edge_mlp3 (5-pack, d = 64,
-    a backend that has it), else None.  DM_NO_FUSED_MLP=1 forces None."""
-    if (d == 64 and hasattr(ops, "r_edge_mlp3")
-            and os.environ.get("DM_NO_FUSED_MLP", "0") != "1"):
-        return _fusedT(packs)
-    return None
+def first3(ops, pd, v, e, packs, d, zh=False):
+    """silu(z) of one MLP's first layer over cat(v[src], v[dst], e), in the
+    autograd forms of the backend: the fused kernel where mlp_path allows
+    (5-pack, frozen), else addmm + gather_add3.  zh: (z, silu(z)), the pair
+    ops.mlp_tail takes."""
+    ws, wd, we, bcg, _, _ = _unpack_edge(packs, d)
+    if not packs[0].requires_grad and mlp_path.fused_first(ops, d):
+        # per-edge GEMM fused into the gather kernel (no [E,2d] transient)
+        f = ops.edge_mlp3_zh if zh else ops.edge_mlp3_act
+        return f(e, packs[4], bcg, v @ ws.t(), v @ wd.t(), pd)
+    f = ops.gather_add3_zh if zh else ops.gather_add3_act
+    return f(v @ ws.t(), v @ wd.t(), torch.addmm(bcg, e, we.t()), pd)
 
 
-def _fused_first_bwd(ops, packs, d):
-    """fusedT when the first layer's reverse can run as r_edge_mlp_bwd,
-    else None.  DM_NO_FUSED_MLP1_BWD=1 forces None (addmm, r_gather_dst)."""
-    if (d == 64 and hasattr(ops, "r_edge_mlp_bwd")
-            and os.environ.get("DM_NO_FUSED_MLP1_BWD", "0") != "1"):
-        return _fusedT(packs)
-    return None
+def first4(ops, pd, n, a, v, packs, d, zh=False):
+    """first3 over cat(n[l_src], n[l_dst], a, v[center])."""
+    w1, wn2, wa, wv, bcg, _, _ = _unpack_line(packs, d)
+    if (not packs[0].requires_grad
+            and mlp_path.fused_first(ops, d, "edge_mlp4_act")):
+        f = ops.edge_mlp4_zh if zh else ops.edge_mlp4_act
+        return f(a, packs[4], bcg, n @ w1.t(), n @ wn2.t(), v @ wv.t(), pd)
+    f = ops.gather_add4_zh if zh else ops.gather_add4_act
+    return f(n @ w1.t(), n @ wn2.t(), torch.addmm(bcg, a, wa.t()),
+             v @ wv.t(), pd)
 
 
 def _first_fwd(ops, pd, v, e, packs, d):
-    """(z, h) of one MLP's first layer over cat(v[src], v[dst], e)."""
+    """(z, h) of one MLP's first layer over cat(v[src], v[dst], e), raw."""
     ws, wd, we, bcg, _, _ = _unpack_edge(packs, d)
-    ft = _fused_first(ops, packs, d)
-    if ft is not None:
+    ft = _fusedT(packs)
+    if ft is not None and mlp_path.fused_first(ops, d, "r_edge_mlp3"):
         return ops.r_edge_mlp3(e, ft, bcg, v @ ws.t(), v @ wd.t(), pd)
     return ops.r_gather_add3(v @ ws.t(), v @ wd.t(),
                              torch.addmm(bcg, e, we.t()), pd)
 
 
-def _fused_full(ops, d, name):
-    """Whether a whole gated MLP can run as the one-kernel primitive `name`
-    (first layer, second layer and combine, no h array): d = 64 and a backend
-    that has it.  DM_NO_FUSED_MLP_FULL=1 restores the first-layer + tail
-    kernel pair; the switches of those two kernels (DM_NO_FUSED_MLP,
-    DM_NO_FUSED_MLP_FWD) turn it off as well."""
-    return (_fused_tail_fwd(ops, d, name)
-            and os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
-            and os.environ.get("DM_NO_FUSED_MLP_FULL", "0") != "1")
-
-
-def _records(*ts):
-    return torch.is_grad_enabled() and any(
-        t is not None and t.requires_grad for t in ts)
+def _fused_first_bwd(ops, packs, d):
+    """fusedT when the first layer's reverse can run as r_edge_mlp_bwd,
+    else None."""
+    return _fusedT(packs) if mlp_path.fused_first_bwd(ops, d) else None
 
 
 def _mlp_fwd(ops, pd, v, ebox, packs, w, base, d, want_out=True):
     """(z, cg, out) of one atom-graph gated MLP in keep form: one kernel
-    where the backend has r_gated_mlp3 (5-pack, d = 64), else the first
-    layer followed by the tail.  ebox is a one-element list holding the
+    where mlp_path allows r_gated_mlp3 (5-pack), else the first layer
+    followed by the tail.  ebox is a one-element list holding the
     MLP's e rows.  want_out=False: out is not needed.  The one-kernel form
     then neither computes it nor reads w and base; the two-kernel path
     empties ebox once the first layer has read the rows, so that a caller
     who dropped its own reference has them freed before the tail."""
     ws, wd, _, bcg, w2, b2 = _unpack_edge(packs, d)
-    ft = _fusedT(packs) if _fused_full(ops, d, "r_gated_mlp3") else None
-    if ft is not None:
+    ft = _fusedT(packs)
+    if ft is not None and mlp_path.whole_mlp_keep(ops, d):
         return ops.r_gated_mlp3(ebox[0], ft, bcg, v @ ws.t(), v @ wd.t(), pd,
                                 w2, b2, w, base, want_out)
     z, h = _first_fwd(ops, pd, v, ebox[0], packs, d)
@@ -179,6 +179,27 @@ def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d,
                             want_out=not saves_only)
     v2 = ops.r_seg_dst(msg, pd, base=v) if not saves_only else None
     return v2, e2, (z1, cg1, z2, cg2)
+
+
+def _node_grad(ops, pd, go_v2, dzs, weights):
+    """go_v2 + sum over the MLPs of seg_src(dz) @ ws + seg_dst(dz) @ wd: the
+    v gradient of an atom conv, every term a fused addmm.  dzs (one dz per
+    (ws, wd) of weights, None to skip) is emptied as it goes, so each dz is
+    freed once consumed when the caller holds no other reference."""
+    gv = go_v2
+    for ws, wd in weights:
+        dz = dzs.pop(0)
+        if dz is None:
+            continue
+        if gv is None:
+            gv = ops.r_seg_src(dz, pd) @ ws
+        elif gv is go_v2:
+            gv = torch.addmm(go_v2, ops.r_seg_src(dz, pd), ws)
+        else:
+            gv.addmm_(ops.r_seg_src(dz, pd), ws)
+        gv.addmm_(ops.r_seg_dst(dz, pd), wd)
+        del dz
+    return gv
 
 
 def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
@@ -211,8 +232,7 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
 
     # node MLP reverse (v2 = v + seg_dst(msg))
     if go_v2 is not None:
-        if (ft2 is not None and getattr(ops, "tail_bwd_indexed", False)
-                and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1"):
+        if ft2 is not None and mlp_path.indexed_tail_bwd(ops, d):
             dz2, dwab = ops.r_mlp_tail_bwd(go_v2, cg2, wab, z2, w22,
                                            pd.dst)     # go_idx
         else:
@@ -249,18 +269,11 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     else:
         ge = torch.addmm(ge2, dz1, we1)
     del ge2
-    if need_gv:
-        # v grad: passthrough + all four per-node GEMM backs, fused
-        gv = torch.addmm(go_v2, ops.r_seg_src(dz1, pd), ws1) \
-            if go_v2 is not None else ops.r_seg_src(dz1, pd) @ ws1
-        gv.addmm_(ops.r_seg_dst(dz1, pd), wd1)
-        del dz1
-        if dz2 is not None:
-            gv.addmm_(ops.r_seg_src(dz2, pd), ws2)
-            gv.addmm_(ops.r_seg_dst(dz2, pd), wd2)
-            del dz2
-    else:
-        gv = None
+    dzs = [dz1, dz2]
+    del dz1, dz2
+    # v grad: passthrough + all four per-node GEMM backs, fused
+    gv = _node_grad(ops, pd, go_v2, dzs, ((ws1, wd1), (ws2, wd2))) \
+        if need_gv else None
     if acc_wbb is not None:
         acc_wbb.add_(dwbb)
         dwbb = None
@@ -301,13 +314,12 @@ class _AtomConvFn(torch.autograd.Function):
         return gv, ge, dwbb, dwab, None, None, None, None, None
 
 
-def conv_fn_available(ops, mlp_pack) -> bool:
-    """Hand-sequenced path policy: frozen weights, raw-primitive backend,
-    recording mode, and explicit opt-in (measured ~1% slower than the
-    op-by-op path after the addmm/materialize fixes — see module
-    docstring)."""
-    return (os.environ.get("DM_FUSED_CONV", "0") == "1"
-            and hasattr(ops, "r_gather_add3")
+def conv_fn_available(ops, mlp_pack, prim="r_gather_add3") -> bool:
+    """Hand-sequenced path policy: frozen weights, a backend with the raw
+    primitive `prim` (r_gather_add4 for the bond conv), recording mode, and
+    explicit opt-in (measured ~1% slower than the op-by-op path after the
+    addmm/materialize fixes — see module docstring)."""
+    return (mlp_path.fused_conv(ops, prim)
             and not mlp_pack[0].requires_grad
             and torch.is_grad_enabled())
 
@@ -315,9 +327,7 @@ def conv_fn_available(ops, mlp_pack) -> bool:
 def bond_fwd(ops, pd, n, a, v, w3, packs, d, mask_l=None):
     """One bond (line-graph) node conv forward (chgnet.py:326-348).
     Returns (n2, saved) with saved = (z, cg, wl)."""
-    wcg, bcg, w2, b2 = packs
-    w1, wn2, wa, wv = (wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:3 * d],
-                       wcg[:, 3 * d:])
+    w1, wn2, wa, wv, bcg, w2, b2 = _unpack_line(packs, d)
     wl = ops.r_gather_lsrc(w3, pd)
     if mask_l is not None:
         wl = wl * mask_l
@@ -333,9 +343,7 @@ def bond_bwd(ops, pd, saved, packs, d, go_n2, mask_l=None,
     """Hand-sequenced reverse of bond_fwd.  Returns (gn, da, gv, gw3);
     da/gv/gw3 are accumulated into acc_* buffers (add_) when given."""
     z, cg, wl = saved
-    wcg, _, w2, _ = packs
-    w1, wn2, wa, wv = (wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:3 * d],
-                       wcg[:, 3 * d:])
+    w1, wn2, wa, wv, _, w2, _ = _unpack_line(packs, d)
     go_n2 = go_n2.contiguous()
     dmsg = ops.r_gather_ldst(go_n2, pd)
     dz, dwl = _mlp_tail_bwd(ops, dmsg, cg, wl, z, w2, d)
@@ -364,9 +372,7 @@ def bond_bwd(ops, pd, saved, packs, d, go_n2, mask_l=None,
 def angle_fwd(ops, pd, n, a, v, packs, d):
     """Angle (line-edge) update forward: a2 = a + GatedMLP(cat(n_lsrc,
     n_ldst, a, v_center)) (chgnet.py:350-368).  Returns (a2, saved)."""
-    wcg, bcg, w2, b2 = packs
-    w1, wn2, wa, wv = (wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:3 * d],
-                       wcg[:, 3 * d:])
+    w1, wn2, wa, wv, bcg, w2, b2 = _unpack_line(packs, d)
     z, h = ops.r_gather_add4(n @ w1.t(), n @ wn2.t(),
                              torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
     cg, a2 = _mlp_tail_fwd(ops, h, w2, b2, None, a, d)
@@ -377,9 +383,7 @@ def angle_bwd(ops, pd, saved, packs, d, go_a2, acc_n=None, acc_v=None):
     """Reverse of angle_fwd.  Returns (gn, da, gv); gn/gv accumulate into
     acc_* when given (da is the full pass-through + wa chain)."""
     z, cg = saved
-    wcg, _, w2, _ = packs
-    w1, wn2, wa, wv = (wcg[:, :d], wcg[:, d:2 * d], wcg[:, 2 * d:3 * d],
-                       wcg[:, 3 * d:])
+    w1, wn2, wa, wv, _, w2, _ = _unpack_line(packs, d)
     go_a2 = go_a2.contiguous()
     dz, _ = _mlp_tail_bwd(ops, go_a2, cg, None, z, w2, d)
     da = torch.addmm(go_a2, dz, wa)
@@ -428,29 +432,19 @@ class _BondConvFn(torch.autograd.Function):
 # Whole-graph hand-sequenced reverse (round-2)
 # ---------------------------------------------------------------------------
 
+def _lean_edge_update(ops, pd, v, e, wbb, pe, d):
+    """e2 only (no z/cg kept) — first half of the atom conv."""
+    return _mlp_tail_act(ops, first3(ops, pd, v, e, pe, d), pe[2], pe[3],
+                         wbb, e, d)
+
+
 def _lean_atom(ops, pd, v, e, wbb, wab, pe, pn, d):
     """Save-nothing atom-conv forward (recompute mode): the fused no-z
     first-layer kernel applies when available, exactly like the
     checkpointed op-by-op outer forward."""
-    wcg1, bcg1, w21, b21, fusedT1 = pe
-    wcg2, bcg2, w22, b22, fusedT2 = pn
-    ws1, wd1 = wcg1[:, :d], wcg1[:, d:2 * d]
-    ws2, wd2 = wcg2[:, :d], wcg2[:, d:2 * d]
-    if d == 64 and hasattr(ops, "edge_mlp3_act"):
-        h1 = ops.edge_mlp3_act(e, fusedT1, bcg1, v @ ws1.t(), v @ wd1.t(), pd)
-    else:
-        h1 = ops.gather_add3_act(v @ ws1.t(), v @ wd1.t(),
-                                 torch.addmm(bcg1, e, wcg1[:, 2 * d:].t()),
-                                 pd)
-    e2 = _mlp_tail_act(ops, h1, w21, b21, wbb, e, d)
-    if d == 64 and hasattr(ops, "edge_mlp3_act"):
-        h2 = ops.edge_mlp3_act(e2, fusedT2, bcg2, v @ ws2.t(), v @ wd2.t(),
-                               pd)
-    else:
-        h2 = ops.gather_add3_act(v @ ws2.t(), v @ wd2.t(),
-                                 torch.addmm(bcg2, e2, wcg2[:, 2 * d:].t()),
-                                 pd)
-    msg = _mlp_tail_act(ops, h2, w22, b22, wab, None, d)
+    e2 = _lean_edge_update(ops, pd, v, e, wbb, pe, d)
+    msg = _mlp_tail_act(ops, first3(ops, pd, v, e2, pn, d), pn[2], pn[3],
+                        wab, None, d)
     return ops.scatter_edges(msg, pd, base=v), e2
 
 
@@ -467,13 +461,9 @@ def _is_factored(w):
 def _factored_w(ops, bexp, d):
     """Whether a block hands its two message weights to the MLP tail kernels
     as factors (ops.RadialW: bexp, W, mask) instead of building the dense
-    [E,d] arrays: a backend that takes them (fp32, d = 64, n_rbf = 9), and the
-    fused tails in use.  DM_NO_FACTORED_W=1 restores the dense weights."""
-    return (getattr(ops, "factored_w", False) and d == 64
-            and bexp.dtype == torch.float32 and bexp.shape[1] == 9
-            and os.environ.get("DM_NO_FACTORED_W", "0") != "1"
-            and os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1"
-            and os.environ.get("DM_NO_FUSED_MLP_BWD", "0") != "1")
+    [E,d] arrays: mlp_path allows it and bexp is fp32 with n_rbf = 9."""
+    return (mlp_path.factored_w(ops, d)
+            and bexp.dtype == torch.float32 and bexp.shape[1] == 9)
 
 
 def _block_weights(ops, bexp, Wbb, Wab, edge_mask, d):
@@ -590,23 +580,12 @@ class _AtomBlockKeepFn(_AtomBlockFn):
         return _AtomBlockFn.forward(ctx, *args)
 
 
-def final_keep_enabled() -> bool:
-    """DM_NO_FINAL_KEEP=1 gives the final block back its recomputation."""
-    return os.environ.get("DM_NO_FINAL_KEEP", "0") != "1"
-
-
 # ---------------------------------------------------------------------------
 # edge <-> bond row exchange of a checkpointed step
 # ---------------------------------------------------------------------------
 
-def row_exchange_enabled() -> bool:
-    """DM_NO_ROW_EXCHANGE=1 restores the two out-of-place index_copy lines
-    of runtime.step."""
-    return os.environ.get("DM_NO_ROW_EXCHANGE", "0") != "1"
-
-
 def _native_rows(ops, *ts):
-    return hasattr(ops, "r_move_rows") and all(
+    return mlp_path.native_rows(ops) and all(
         t.is_cuda and t.dtype == torch.float32 for t in ts)
 
 
@@ -712,55 +691,33 @@ def bond_to_edge(e, n2, pd, ops):
 
 
 def atom_block_available(ops, pe, d, dtype) -> bool:
-    """Self-recomputing block policy for checkpointed steps: fp32, d = 64,
-    frozen weights, recording mode, a backend with the raw fused first
-    layer and its reverse.  DM_NO_ATOM_BLOCK=1 keeps torch.utils.checkpoint
-    around the op-by-op block; DM_FUSED_CONV=1 and DM_NO_FUSED_MLP=1 keep
-    their own paths."""
-    return (os.environ.get("DM_NO_ATOM_BLOCK", "0") != "1"
-            and os.environ.get("DM_FUSED_CONV", "0") != "1"
-            and os.environ.get("DM_NO_FUSED_MLP", "0") != "1"
-            and d == 64 and dtype == torch.float32
-            and hasattr(ops, "r_edge_mlp3") and hasattr(ops, "r_edge_mlp_bwd")
-            and hasattr(ops, "edge_mlp3_act")
+    """Self-recomputing block policy for checkpointed steps: fp32, frozen
+    weights, recording mode, and mlp_path.atom_block (d = 64, a backend
+    with the raw fused first layer and its reverse, no switch against it)."""
+    return (mlp_path.atom_block(ops, d) and dtype == torch.float32
             and not pe[0].requires_grad
             and torch.is_grad_enabled())
 
 
+def _lean_line(ops, pd, n, a, v, packs, d, w, base):
+    """Save-nothing line-graph gated MLP: one kernel where mlp_path allows
+    gated_mlp4_act and nothing records, else first layer + tail."""
+    if mlp_path.whole_mlp_act(ops, d) and not _records(n, a, v, w):
+        w1, wn2, _, wv, bcg, w2, b2 = _unpack_line(packs, d)
+        return ops.gated_mlp4_act(a, packs[4], bcg, n @ w1.t(), n @ wn2.t(),
+                                  v @ wv.t(), pd, w2, b2, w, base)
+    return _mlp_tail_act(ops, first4(ops, pd, n, a, v, packs, d), packs[2],
+                         packs[3], w, base, d)
+
+
 def _lean_bond(ops, pd, n, a, v, w3, pb, d):
-    wcg, bcg, w2, b2, fusedT = pb
-    w1, wn2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
     wl = ops.gather(w3, pd.l_src, csr=pd.line_src_csr)
-    if (_fused_full(ops, d, "gated_mlp4_act")
-            and not _records(n, a, v, wl)):
-        msg = ops.gated_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
-                                 v @ wv.t(), pd, w2, b2, wl, None)
-        return ops.scatter_lines(msg, pd, base=n)
-    if d == 64 and hasattr(ops, "edge_mlp4_act"):
-        h = ops.edge_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
-                              v @ wv.t(), pd)
-    else:
-        h = ops.gather_add4_act(n @ w1.t(), n @ wn2.t(),
-                                torch.addmm(bcg, a, wcg[:, 2 * d:3 * d].t()),
-                                v @ wv.t(), pd)
-    msg = _mlp_tail_act(ops, h, w2, b2, wl, None, d)
-    return ops.scatter_lines(msg, pd, base=n)
+    return ops.scatter_lines(_lean_line(ops, pd, n, a, v, pb, d, wl, None),
+                             pd, base=n)
 
 
 def _lean_angle(ops, pd, n, a, v, pa, d):
-    wcg, bcg, w2, b2, fusedT = pa
-    w1, wn2, wv = wcg[:, :d], wcg[:, d:2 * d], wcg[:, 3 * d:]
-    if (_fused_full(ops, d, "gated_mlp4_act") and not _records(n, a, v)):
-        return ops.gated_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
-                                  v @ wv.t(), pd, w2, b2, None, a)
-    if d == 64 and hasattr(ops, "edge_mlp4_act"):
-        h = ops.edge_mlp4_act(a, fusedT, bcg, n @ w1.t(), n @ wn2.t(),
-                              v @ wv.t(), pd)
-    else:
-        h = ops.gather_add4_act(n @ w1.t(), n @ wn2.t(),
-                                torch.addmm(bcg, a, wcg[:, 2 * d:3 * d].t()),
-                                v @ wv.t(), pd)
-    return _mlp_tail_act(ops, h, w2, b2, None, a, d)
+    return _lean_line(ops, pd, n, a, v, pa, d, None, a)
 
 
 def _edge_to_bond(pd, n, e):
@@ -770,11 +727,11 @@ def _edge_to_bond(pd, n, e):
 def _keep_packs(pe, pn):
     """The atom packs _WholeGraphFn's keep mode hands to atom_fwd /
     atom_bwd: with fusedT, so the fused first layer and its reverse kernels
-    run; DM_NO_ATOM_BLOCK=1 restores the 4-packs (rocBLAS first layer), as
-    it restores the checkpointed steps' op-by-op blocks."""
-    if os.environ.get("DM_NO_ATOM_BLOCK", "0") == "1":
-        return pe[:4], pn[:4]
-    return pe, pn
+    run, unless mlp_path.fused_keep_packs says the 4-packs (rocBLAS first
+    layer)."""
+    if mlp_path.fused_keep_packs():
+        return pe, pn
+    return pe[:4], pn[:4]
 
 
 class _WholeGraphFn(torch.autograd.Function):
@@ -967,27 +924,11 @@ class _WholeGraphFn(torch.autograd.Function):
 
 def whole_graph_available(ops, mlp_pack) -> bool:
     """Whole-graph sequenced-reverse policy: single partition, frozen
-    weights, raw-primitive backend, recording mode.  Default follows the
-    measured A/B (DM_WHOLE_GRAPH=1/0 overrides)."""
-    default = "1"          # keep-mode measured win (runtime gates ckpt mode)
-    return (os.environ.get("DM_WHOLE_GRAPH", default) == "1"
-            and hasattr(ops, "r_gather_add3")
+    weights, raw-primitive backend, recording mode.  On by default: the
+    keep mode is a measured win (runtime gates the checkpointed mode)."""
+    return (mlp_path.whole_graph(ops)
             and not mlp_pack[0].requires_grad
             and torch.is_grad_enabled())
-
-
-def _lean_edge_update(ops, pd, v, e, wbb, pe, d):
-    """e2 only (no z/cg kept) — first half of the atom conv."""
-    wcg1, bcg1, w21, b21, fusedT1 = pe
-    ws1, wd1 = wcg1[:, :d], wcg1[:, d:2 * d]
-    if d == 64 and hasattr(ops, "edge_mlp3_act"):
-        h1 = ops.edge_mlp3_act(e, fusedT1, bcg1, v @ ws1.t(), v @ wd1.t(),
-                               pd)
-    else:
-        h1 = ops.gather_add3_act(v @ ws1.t(), v @ wd1.t(),
-                                 torch.addmm(bcg1, e, wcg1[:, 2 * d:].t()),
-                                 pd)
-    return _mlp_tail_act(ops, h1, w21, b21, wbb, e, d)
 
 
 def atom_bwd_recompute(ops, pd, v_in, e_in, wbb, wab, pe, pn, d,
@@ -1030,14 +971,9 @@ def atom_bwd_recompute(ops, pd, v_in, e_in, wbb, wab, pe, pn, d,
     del cg1, z1
     ge = torch.addmm(ge2, dz1, we1)
     del ge2
-    gv = torch.addmm(go_v2, ops.r_seg_src(dz1, pd), ws1) \
-        if go_v2 is not None else ops.r_seg_src(dz1, pd) @ ws1
-    gv.addmm_(ops.r_seg_dst(dz1, pd), wd1)
-    del dz1
-    if dz2 is not None:
-        gv.addmm_(ops.r_seg_src(dz2, pd), ws2)
-        gv.addmm_(ops.r_seg_dst(dz2, pd), wd2)
-        del dz2
+    dzs = [dz1, dz2]
+    del dz1, dz2
+    gv = _node_grad(ops, pd, go_v2, dzs, ((ws1, wd1), (ws2, wd2)))
     acc_wbb.add_(dwbb)
     del dwbb
     return gv, ge

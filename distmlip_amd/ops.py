@@ -13,11 +13,11 @@ device — there is no fallback.
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_uint64
 
 import torch
 
+from distmlip_amd import mlp_path
 from distmlip_amd.capi import _load
 
 _hip_lib = None
@@ -204,11 +204,23 @@ def hip_lib() -> ctypes.CDLL:
 
 
 def _fp(t):
-    return ctypes.cast(t.data_ptr(), POINTER(c_float))
+    return ctypes.cast(t.data_ptr(), POINTER(c_float)) if t is not None \
+        else None
 
 
 def _ip(t):
-    return ctypes.cast(t.data_ptr(), POINTER(c_int32))
+    return ctypes.cast(t.data_ptr(), POINTER(c_int32)) if t is not None \
+        else None
+
+
+def _halves(t):
+    """The pointers to t[0] and t[1] of a packed contiguous fp32 [2, ...]
+    tensor (cg, w2, b2); (None, None) for None."""
+    if t is None:
+        return None, None
+    p = t.data_ptr()
+    return (ctypes.cast(p, POINTER(c_float)),
+            ctypes.cast(p + 2 * t.numel(), POINTER(c_float)))
 
 
 def _hp(t):
@@ -293,8 +305,7 @@ def raw_seg_sum(msg, row_ptr, n_rows, base=None):
     out = torch.empty((n_rows,) + tuple(msg.shape[1:]), dtype=msg.dtype,
                       device=msg.device)
     _check(hip_lib().dm_seg_sum_f32(
-        _fp(msg), _ip(row_ptr), _fp(base) if base is not None else None,
-        _fp(out), n_rows, msg.shape[1], _stream()), "dm_seg_sum_f32")
+        _fp(msg), _ip(row_ptr), _fp(base), _fp(out), n_rows, msg.shape[1], _stream()), "dm_seg_sum_f32")
     return out
 
 
@@ -303,8 +314,7 @@ def raw_seg_sum_gather(msg, perm, row_ptr, n_rows, base=None):
     out = torch.empty((n_rows,) + tuple(msg.shape[1:]), dtype=msg.dtype,
                       device=msg.device)
     _check(hip_lib().dm_seg_sum_gather_f32(
-        _fp(msg), _ip(perm), _ip(row_ptr),
-        _fp(base) if base is not None else None, _fp(out), n_rows,
+        _fp(msg), _ip(perm), _ip(row_ptr), _fp(base), _fp(out), n_rows,
         msg.shape[1], _stream()), "dm_seg_sum_gather_f32")
     return out
 
@@ -331,8 +341,8 @@ def raw_silu_bwd(go_h, go_z, z):
     """dz = (go_z or 0) + go_h * silu'(z), one fused pass."""
     dz = torch.empty_like(z)
     _check(hip_lib().dm_silu_bwd_f32(
-        _fp(go_h), _fp(go_z) if go_z is not None else None, _fp(z), _fp(dz),
-        z.numel(), _stream()), "dm_silu_bwd_f32")
+        _fp(go_h), _fp(go_z), _fp(z), _fp(dz), z.numel(), _stream()),
+        "dm_silu_bwd_f32")
     return dz
 
 
@@ -366,53 +376,99 @@ def raw_act_eval(which: int, x: torch.Tensor, ref: bool) -> torch.Tensor:
     return out
 
 
+def _dz_of(go_z, go_h, z):
+    """The gradient on z of a first layer that returned (z, silu(z))."""
+    if go_h is None:
+        return go_z.contiguous()
+    return raw_silu_bwd(go_h.contiguous(), _cont(go_z), z)
+
+
+def _edge_seg_sums(dz, src_perm, src_row_ptr, row_ptr, n_nodes):
+    """dz summed onto the src and the dst table of the atom graph."""
+    return (raw_seg_sum_gather(dz, src_perm, src_row_ptr, n_nodes),
+            raw_seg_sum(dz, row_ptr, n_nodes))
+
+
+def _line_seg_sums(dz, pd, n_bonds, n_nodes):
+    """dz summed onto the l_src, l_dst and center tables of the line graph."""
+    return (raw_seg_sum_gather(dz, pd.line_src_perm, pd.line_src_row_ptr,
+                               n_bonds),
+            raw_seg_sum(dz, pd.line_row_ptr, n_bonds),
+            raw_seg_sum_gather(dz, pd.center_perm, pd.center_row_ptr,
+                               n_nodes))
+
+
+def _grad_inputs(*ts):
+    return any(t.requires_grad for t in ts)
+
+
+def raw_gather_add3(zs, zd, ze, src, dst, inplace=False):
+    """(z, silu(z)) with z = zs[src] + zd[dst] + ze in one kernel.  inplace:
+    silu goes over z (the kernel writes z then silu(z) per element, so one
+    buffer is safe and halves the transient footprint) and z is h."""
+    _chk_f32(zs, zd, ze)
+    z = torch.empty_like(ze)
+    h = z if inplace else torch.empty_like(ze)
+    _check(hip_lib().dm_gather_add3_f32(
+        _fp(zs), _fp(zd), _fp(ze), _ip(src), _ip(dst), _fp(z), _fp(h),
+        ze.shape[0], ze.shape[1], _stream()), "dm_gather_add3_f32")
+    return z, h
+
+
+def raw_gather_add4(z1, z2, za, zv, pd, inplace=False):
+    """raw_gather_add3 over the line graph's three gathers."""
+    _chk_f32(z1, z2, za, zv)
+    z = torch.empty_like(za)
+    h = z if inplace else torch.empty_like(za)
+    _check(hip_lib().dm_gather_add4_f32(
+        _fp(z1), _fp(z2), _fp(za), _fp(zv), _ip(pd.l_src), _ip(pd.l_dst),
+        _ip(pd.center), _fp(z), _fp(h), za.shape[0], za.shape[1],
+        _stream()), "dm_gather_add4_f32")
+    return z, h
+
+
+def raw_edge_mlp3(erow, wt, bias, zs, zd, src, dst, keep_z=True):
+    """(z, silu(z)) with z = erow @ wt + bias + zs[src] + zd[dst], the
+    per-edge GEMM inside the gather kernel (wt = the [64,128] fusedT pack).
+    keep_z=False skips the z write; z is then empty."""
+    _chk_f32(erow, wt, bias, zs, zd)
+    E, dout = erow.shape[0], wt.shape[1]
+    h = torch.empty(E, dout, dtype=erow.dtype, device=erow.device)
+    z = torch.empty_like(h) if keep_z else h[:0]
+    _check(hip_lib().dm_edge_mlp3_f32(
+        _fp(erow), _fp(wt), _fp(bias), _fp(zs), _fp(zd), _ip(src), _ip(dst),
+        _fp(z) if keep_z else None, _fp(h), E, wt.shape[0], dout, _stream()),
+        "dm_edge_mlp3_f32")
+    return z, h
+
+
 class _GatherAdd3(torch.autograd.Function):
     """Emits (z, silu(z)) in one kernel; z doubles as the saved activation
     for the fused silu backward."""
 
     @staticmethod
     def forward(ctx, zs, zd, ze, src, dst, src_perm, src_row_ptr, row_ptr):
-        _chk_f32(zs, zd, ze)
         # the z output is usually discarded (only h flows on): without this,
         # autograd materializes a full [E,2d] ZERO go_z every backward (a
         # zero-fill write + an extra read inside silu_bwd, ~0.8 ms/call at
         # li100k, rocprof run 17)
         ctx.set_materialize_grads(False)
         ctx.n_nodes = zs.shape[0]
-        z = torch.empty_like(ze)
         # grad mode is always OFF inside Function.forward, so test the
         # inputs: when none requires grad (checkpoint outer pass /
-        # inference) no backward will run and silu can go in place over z —
-        # the kernel writes z then silu(z) per element, so a single buffer
-        # is safe and halves the transient footprint
-        if zs.requires_grad or zd.requires_grad or ze.requires_grad:
-            h = torch.empty_like(ze)
-        else:
-            h = z
-        _check(hip_lib().dm_gather_add3_f32(
-            _fp(zs), _fp(zd), _fp(ze), _ip(src), _ip(dst), _fp(z), _fp(h),
-            ze.shape[0], ze.shape[1], _stream()), "dm_gather_add3_f32")
+        # inference) no backward will run and silu can go in place over z
+        z, h = raw_gather_add3(zs, zd, ze, src, dst,
+                               inplace=not _grad_inputs(zs, zd, ze))
         ctx.save_for_backward(src_perm, src_row_ptr, row_ptr, z)
         return z, h
 
     @staticmethod
     def backward(ctx, go_z, go_h):
         src_perm, src_row_ptr, row_ptr, z = ctx.saved_tensors
-        if go_h is not None:
-            dz = raw_silu_bwd(go_h.contiguous(),
-                              go_z.contiguous() if go_z is not None else None,
-                              z)
-        else:
-            dz = go_z.contiguous()
-        gzs = raw_seg_sum_gather(dz, src_perm, src_row_ptr, ctx.n_nodes)
-        gzd = raw_seg_sum(dz, row_ptr, ctx.n_nodes)
+        dz = _dz_of(go_z, go_h, z)
+        gzs, gzd = _edge_seg_sums(dz, src_perm, src_row_ptr, row_ptr,
+                                  ctx.n_nodes)
         return gzs, gzd, dz, None, None, None, None, None
-
-
-def use_fused_mlp1_bwd() -> bool:
-    """First-layer reverse kernel switch: DM_NO_FUSED_MLP1_BWD=1 restores
-    the rocBLAS GEMM / addmm everywhere, for A/B runs in one build."""
-    return os.environ.get("DM_NO_FUSED_MLP1_BWD", "0") != "1"
 
 
 def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None):
@@ -429,17 +485,16 @@ def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None):
         out = torch.empty(E, wt.shape[0], dtype=dz.dtype, device=dz.device)
     assert out.shape == (E, wt.shape[0])
     _check(hip_lib().dm_edge_mlp_bwd_f32(
-        _fp(dz), _fp(wt), _fp(gbase) if gbase is not None else None,
-        _fp(out), E, dz.shape[1], wt.shape[0], _stream()),
-        "dm_edge_mlp_bwd_f32")
+        _fp(dz), _fp(wt), _fp(gbase), _fp(out), E, dz.shape[1], wt.shape[0],
+        _stream()), "dm_edge_mlp_bwd_f32")
     return out
 
 
 def _first_layer_de(dz, wt):
-    """dz @ wt.t(): dm_edge_mlp_bwd_f32 for the [64,128] pack, else (or
-    with DM_NO_FUSED_MLP1_BWD=1) rocBLAS."""
+    """dz @ wt.t(): dm_edge_mlp_bwd_f32 for the [64,128] pack where
+    mlp_path allows it, else rocBLAS."""
     if (tuple(wt.shape) == (64, 128) and dz.dtype == torch.float32
-            and use_fused_mlp1_bwd()):
+            and mlp_path.fused_first_bwd(HipOps, wt.shape[0])):
         return raw_edge_mlp_bwd(dz, wt)
     return dz @ wt.t()
 
@@ -455,33 +510,22 @@ class _EdgeMlp3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, erow, wt, bias, zs, zd, src, dst, src_perm, src_row_ptr,
                 row_ptr):
-        _chk_f32(erow, wt, bias, zs, zd)
         assert not wt.requires_grad and not bias.requires_grad
         ctx.set_materialize_grads(False)
         ctx.n_nodes = zs.shape[0]
-        E, dout = erow.shape[0], wt.shape[1]
-        h = torch.empty(E, dout, dtype=erow.dtype, device=erow.device)
-        needs_z = erow.requires_grad or zs.requires_grad or zd.requires_grad
-        z = torch.empty_like(h) if needs_z else h[:0]  # no bwd: skip z write
-        _check(hip_lib().dm_edge_mlp3_f32(
-            _fp(erow), _fp(wt), _fp(bias), _fp(zs), _fp(zd), _ip(src),
-            _ip(dst), _fp(z) if needs_z else None, _fp(h), E, wt.shape[0],
-            dout, _stream()), "dm_edge_mlp3_f32")
+        # no backward: skip the z write
+        z, h = raw_edge_mlp3(erow, wt, bias, zs, zd, src, dst,
+                             keep_z=_grad_inputs(erow, zs, zd))
         ctx.save_for_backward(src_perm, src_row_ptr, row_ptr, z, wt)
         return z, h
 
     @staticmethod
     def backward(ctx, go_z, go_h):
         src_perm, src_row_ptr, row_ptr, z, wt = ctx.saved_tensors
-        if go_h is not None:
-            dz = raw_silu_bwd(go_h.contiguous(),
-                              go_z.contiguous() if go_z is not None else None,
-                              z)
-        else:
-            dz = go_z.contiguous()
+        dz = _dz_of(go_z, go_h, z)
         de = _first_layer_de(dz, wt)
-        gzs = raw_seg_sum_gather(dz, src_perm, src_row_ptr, ctx.n_nodes)
-        gzd = raw_seg_sum(dz, row_ptr, ctx.n_nodes)
+        gzs, gzd = _edge_seg_sums(dz, src_perm, src_row_ptr, row_ptr,
+                                  ctx.n_nodes)
         return de, None, None, gzs, gzd, None, None, None, None, None
 
 
@@ -499,8 +543,7 @@ class _EdgeMlp4(torch.autograd.Function):
         ctx.n_nodes = zv.shape[0]
         L, dout = arow.shape[0], wt.shape[1]
         h = torch.empty(L, dout, dtype=arow.dtype, device=arow.device)
-        needs_z = (arow.requires_grad or z1.requires_grad or z2.requires_grad
-                   or zv.requires_grad)
+        needs_z = _grad_inputs(arow, z1, z2, zv)
         z = torch.empty_like(h) if needs_z else h[:0]
         _check(hip_lib().dm_edge_mlp4_f32(
             _fp(arow), _fp(wt), _fp(bias), _fp(z1), _fp(z2), _fp(zv),
@@ -512,20 +555,10 @@ class _EdgeMlp4(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, go_z, go_h):
-        pd = ctx.pd
         z, wt = ctx.saved_tensors
-        if go_h is not None:
-            dz = raw_silu_bwd(go_h.contiguous(),
-                              go_z.contiguous() if go_z is not None else None,
-                              z)
-        else:
-            dz = go_z.contiguous()
+        dz = _dz_of(go_z, go_h, z)
         da = _first_layer_de(dz, wt)
-        gz1 = raw_seg_sum_gather(dz, pd.line_src_perm, pd.line_src_row_ptr,
-                                 ctx.n_bonds)
-        gz2 = raw_seg_sum(dz, pd.line_row_ptr, ctx.n_bonds)
-        gzv = raw_seg_sum_gather(dz, pd.center_perm, pd.center_row_ptr,
-                                 ctx.n_nodes)
+        gz1, gz2, gzv = _line_seg_sums(dz, ctx.pd, ctx.n_bonds, ctx.n_nodes)
         return da, None, None, gz1, gz2, gzv, None
 
 
@@ -534,38 +567,21 @@ class _GatherAdd4(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z1, z2, za, zv, pd):
-        _chk_f32(z1, z2, za, zv)
         ctx.set_materialize_grads(False)   # see _GatherAdd3.forward
         ctx.pd = pd
         ctx.n_bonds = z1.shape[0]
         ctx.n_nodes = zv.shape[0]
-        z = torch.empty_like(za)
         # see _GatherAdd3.forward: in-place silu only when no backward runs
-        needs_h = (z1.requires_grad or z2.requires_grad or za.requires_grad
-                   or zv.requires_grad)
-        h = torch.empty_like(za) if needs_h else z
-        _check(hip_lib().dm_gather_add4_f32(
-            _fp(z1), _fp(z2), _fp(za), _fp(zv), _ip(pd.l_src), _ip(pd.l_dst),
-            _ip(pd.center), _fp(z), _fp(h), za.shape[0], za.shape[1],
-            _stream()), "dm_gather_add4_f32")
+        z, h = raw_gather_add4(z1, z2, za, zv, pd,
+                               inplace=not _grad_inputs(z1, z2, za, zv))
         ctx.save_for_backward(z)
         return z, h
 
     @staticmethod
     def backward(ctx, go_z, go_h):
-        pd = ctx.pd
         (z,) = ctx.saved_tensors
-        if go_h is not None:
-            dz = raw_silu_bwd(go_h.contiguous(),
-                              go_z.contiguous() if go_z is not None else None,
-                              z)
-        else:
-            dz = go_z.contiguous()
-        gz1 = raw_seg_sum_gather(dz, pd.line_src_perm, pd.line_src_row_ptr,
-                                 ctx.n_bonds)
-        gz2 = raw_seg_sum(dz, pd.line_row_ptr, ctx.n_bonds)
-        gzv = raw_seg_sum_gather(dz, pd.center_perm, pd.center_row_ptr,
-                                 ctx.n_nodes)
+        dz = _dz_of(go_z, go_h, z)
+        gz1, gz2, gzv = _line_seg_sums(dz, ctx.pd, ctx.n_bonds, ctx.n_nodes)
         return gz1, gz2, dz, gzv, None
 
 
@@ -577,7 +593,7 @@ class _SegSum(torch.autograd.Function):
         ctx.save_for_backward(idx)
         ctx.has_base = base is not None
         return raw_seg_sum(msg.contiguous(), row_ptr, n_rows,
-                           base.contiguous() if base is not None else None)
+                           _cont(base))
 
     @staticmethod
     def backward(ctx, grad):
@@ -587,38 +603,54 @@ class _SegSum(torch.autograd.Function):
         return gmsg, None, None, None, gbase
 
 
+def _combine_fwd(c_ptr, g_ptr, w, base, out):
+    """out = base + silu(c) * sigmoid(g) * w over out.numel() elements."""
+    _check(hip_lib().dm_gated_combine_fwd_f32(
+        c_ptr, g_ptr, _fp(w), _fp(base), _fp(out), out.numel(), _stream()),
+        "dm_gated_combine_fwd_f32")
+    return out
+
+
+def _combine_bwd(go, c_ptr, g_ptr, w, dc_ptr, dg_ptr):
+    """Writes dc and dg through their pointers; returns dw (None without w)."""
+    dw = torch.empty_like(w) if w is not None else None
+    _check(hip_lib().dm_gated_combine_bwd_f32(
+        _fp(go), c_ptr, g_ptr, _fp(w), dc_ptr, dg_ptr, _fp(dw), go.numel(),
+        _stream()), "dm_gated_combine_bwd_f32")
+    return dw
+
+
+def raw_combine_fwd(cg, w, base):
+    """base + silu(cg[0]) * sigmoid(cg[1]) * w over packed cg [2,E,D]."""
+    _chk_f32(cg, w, base)
+    return _combine_fwd(*_halves(cg), w, base, torch.empty(
+        cg.shape[1], cg.shape[2], dtype=cg.dtype, device=cg.device))
+
+
+def raw_combine_bwd(go, cg, w):
+    """(dcg [2,E,D] packed, dw) from the gradient go of raw_combine_fwd."""
+    _chk_f32(go, cg, w)
+    dcg = torch.empty_like(cg)
+    return dcg, _combine_bwd(go, *_halves(cg), w, *_halves(dcg))
+
+
 class _GatedCombine(torch.autograd.Function):
     """out = base + silu(c) * sigmoid(g) * w — fused gated-MLP epilogue."""
 
     @staticmethod
     def forward(ctx, c, g, w, base):
         _chk_f32(c, g, w, base)
-        ctx.save_for_backward(c, g) if w is None else \
-            ctx.save_for_backward(c, g, w)
-        ctx.has_w = w is not None
+        ctx.save_for_backward(c, g, w)
         ctx.has_base = base is not None
-        out = torch.empty_like(c)
-        _check(hip_lib().dm_gated_combine_fwd_f32(
-            _fp(c), _fp(g), _fp(w) if w is not None else None,
-            _fp(base) if base is not None else None, _fp(out), c.numel(),
-            _stream()), "dm_gated_combine_fwd_f32")
-        return out
+        return _combine_fwd(_fp(c), _fp(g), w, base, torch.empty_like(c))
 
     @staticmethod
     def backward(ctx, go):
-        if ctx.has_w:
-            c, g, w = ctx.saved_tensors
-        else:
-            c, g = ctx.saved_tensors
-            w = None
+        c, g, w = ctx.saved_tensors
         go = go.contiguous()
         dc = torch.empty_like(c)
         dg = torch.empty_like(g)
-        dw = torch.empty_like(w) if ctx.has_w else None
-        _check(hip_lib().dm_gated_combine_bwd_f32(
-            _fp(go), _fp(c), _fp(g), _fp(w) if w is not None else None,
-            _fp(dc), _fp(dg), _fp(dw) if dw is not None else None,
-            c.numel(), _stream()), "dm_gated_combine_bwd_f32")
+        dw = _combine_bwd(go, _fp(c), _fp(g), w, _fp(dc), _fp(dg))
         return dc, dg, dw, (go if ctx.has_base else None)
 
 
@@ -692,40 +724,15 @@ class _GatedCombinePacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cg, w, base):
-        _chk_f32(cg, w, base)
-        half = cg.shape[1] * cg.shape[2]
-        c_ptr = ctypes.cast(cg.data_ptr(), POINTER(c_float))
-        g_ptr = ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float))
-        out = torch.empty(cg.shape[1], cg.shape[2], dtype=cg.dtype,
-                          device=cg.device)
-        _check(hip_lib().dm_gated_combine_fwd_f32(
-            c_ptr, g_ptr, _fp(w) if w is not None else None,
-            _fp(base) if base is not None else None, _fp(out), half,
-            _stream()), "dm_gated_combine_fwd_f32")
-        ctx.save_for_backward(cg, w) if w is not None else             ctx.save_for_backward(cg)
-        ctx.has_w = w is not None
+        ctx.save_for_backward(cg, w)
         ctx.has_base = base is not None
-        return out
+        return raw_combine_fwd(cg, w, base)
 
     @staticmethod
     def backward(ctx, go):
-        if ctx.has_w:
-            cg, w = ctx.saved_tensors
-        else:
-            (cg,) = ctx.saved_tensors
-            w = None
+        cg, w = ctx.saved_tensors
         go = go.contiguous()
-        half = cg.shape[1] * cg.shape[2]
-        dcg = torch.empty_like(cg)
-        c_ptr = ctypes.cast(cg.data_ptr(), POINTER(c_float))
-        g_ptr = ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float))
-        dc_ptr = ctypes.cast(dcg.data_ptr(), POINTER(c_float))
-        dg_ptr = ctypes.cast(dcg.data_ptr() + 4 * half, POINTER(c_float))
-        dw = torch.empty_like(w) if ctx.has_w else None
-        _check(hip_lib().dm_gated_combine_bwd_f32(
-            _fp(go), c_ptr, g_ptr, _fp(w) if w is not None else None,
-            dc_ptr, dg_ptr, _fp(dw) if dw is not None else None, half,
-            _stream()), "dm_gated_combine_bwd_f32")
+        dcg, dw = raw_combine_bwd(go, cg, w)
         return dcg, dw, (go if ctx.has_base else None)
 
 
@@ -762,43 +769,12 @@ class RadialW:
             or self.dbexp_acc.shape == self.bexp.shape
 
     def ptrs(self):
-        return (_fp(self.bexp), _fp(self.W),
-                _fp(self.mask) if self.mask is not None else None)
+        return _fp(self.bexp), _fp(self.W), _fp(self.mask)
 
 
-def use_factored_w() -> bool:
-    """Factored message weights switch: DM_NO_FACTORED_W=1 restores the dense
-    [E,d] weights (bexp @ W.t() by rocBLAS) everywhere, for A/B runs in one
-    build."""
-    return os.environ.get("DM_NO_FACTORED_W", "0") != "1"
-
-
-def _raw_mlp_tail_bwd_fw(go, cg, rw, z, w2, go_idx):
-    """raw_mlp_tail_bwd with a RadialW: (dz, dbexp)."""
-    _chk_f32(go, cg, z, w2)
-    d = go.shape[1]
-    E = go.shape[0] if go_idx is None else go_idx.shape[0]
-    assert cg.shape == (2, E, d) and z.shape == (E, 2 * d)
-    assert w2.shape == (2, d, d)
-    rw.check(E, d)
-    if go_idx is not None:
-        assert go_idx.dtype == torch.int32 and go_idx.is_contiguous() \
-            and go_idx.device == go.device
-    half = E * d
-    dz = torch.empty_like(z)
-    acc = rw.dbexp_acc
-    dbexp = acc if acc is not None else torch.empty_like(rw.bexp)
-    bexp_p, W_p, mask_p = rw.ptrs()
-    _check(hip_lib().dm_gated_mlp_tail_bwd_fw_f32(
-        _fp(go), _ip(go_idx) if go_idx is not None else None,
-        ctypes.cast(cg.data_ptr(), POINTER(c_float)),
-        ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
-        bexp_p, W_p, mask_p, _fp(z),
-        ctypes.cast(w2.data_ptr(), POINTER(c_float)),
-        ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
-        _fp(dz), _fp(acc) if acc is not None else None, _fp(dbexp), E, d,
-        rw.bexp.shape[1], _stream()), "dm_gated_mlp_tail_bwd_fw_f32")
-    return dz, dbexp
+def _split_w(w):
+    """(dense w or None, RadialW or None) of a tail's w argument."""
+    return (None, w) if isinstance(w, RadialW) else (w, None)
 
 
 def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None):
@@ -809,44 +785,36 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None):
     (int32 [E]) go is a [N,d] table and row r takes go[go_idx[r]]: the
     result on the materialized go[go_idx], without that gather.
     w may be a RadialW: (dz, dbexp) is returned then."""
-    if isinstance(w, RadialW):
-        return _raw_mlp_tail_bwd_fw(go, cg, w, z, w2, go_idx)
+    w, rw = _split_w(w)
     _chk_f32(go, cg, w, z, w2)
     d = go.shape[1]
     E = go.shape[0] if go_idx is None else go_idx.shape[0]
     assert cg.shape == (2, E, d) and z.shape == (E, 2 * d)
     assert w2.shape == (2, d, d) and (w is None or w.shape == (E, d))
-    half = E * d
-    dz = torch.empty_like(z)
-    dw = torch.empty_like(w) if w is not None else None
     if go_idx is not None:
         assert go_idx.dtype == torch.int32 and go_idx.is_contiguous() \
             and go_idx.device == go.device
-        _check(hip_lib().dm_gated_mlp_tail_bwd_idx_f32(
-            _fp(go), _ip(go_idx),
-            ctypes.cast(cg.data_ptr(), POINTER(c_float)),
-            ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
-            _fp(w) if w is not None else None, _fp(z),
-            ctypes.cast(w2.data_ptr(), POINTER(c_float)),
-            ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
-            _fp(dz), _fp(dw) if dw is not None else None, E, d, _stream()),
-            "dm_gated_mlp_tail_bwd_idx_f32")
-        return dz, dw
-    _check(hip_lib().dm_gated_mlp_tail_bwd_f32(
-        _fp(go), ctypes.cast(cg.data_ptr(), POINTER(c_float)),
-        ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
-        _fp(w) if w is not None else None, _fp(z),
-        ctypes.cast(w2.data_ptr(), POINTER(c_float)),
-        ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
-        _fp(dz), _fp(dw) if dw is not None else None, E, d, _stream()),
-        "dm_gated_mlp_tail_bwd_f32")
+    dz = torch.empty_like(z)
+    lib = hip_lib()
+    if rw is not None:
+        rw.check(E, d)
+        acc = rw.dbexp_acc
+        dbexp = acc if acc is not None else torch.empty_like(rw.bexp)
+        _check(lib.dm_gated_mlp_tail_bwd_fw_f32(
+            _fp(go), _ip(go_idx), *_halves(cg), *rw.ptrs(), _fp(z),
+            *_halves(w2), _fp(dz), _fp(acc), _fp(dbexp), E, d,
+            rw.bexp.shape[1], _stream()), "dm_gated_mlp_tail_bwd_fw_f32")
+        return dz, dbexp
+    dw = torch.empty_like(w) if w is not None else None
+    rest = (*_halves(cg), _fp(w), _fp(z), *_halves(w2), _fp(dz), _fp(dw), E,
+            d, _stream())
+    if go_idx is not None:
+        _check(lib.dm_gated_mlp_tail_bwd_idx_f32(_fp(go), _ip(go_idx), *rest),
+               "dm_gated_mlp_tail_bwd_idx_f32")
+    else:
+        _check(lib.dm_gated_mlp_tail_bwd_f32(_fp(go), *rest),
+               "dm_gated_mlp_tail_bwd_f32")
     return dz, dw
-
-
-def use_fused_tail_fwd() -> bool:
-    """Forward-tail kernel switch: DM_NO_FUSED_MLP_FWD=1 restores baddbmm +
-    dm_gated_combine_fwd_f32 everywhere, for A/B runs in one build."""
-    return os.environ.get("DM_NO_FUSED_MLP_FWD", "0") != "1"
 
 
 def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
@@ -856,51 +824,27 @@ def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
     b2 [2,1,d], w and base [E,d] or None.  cg [2,E,d] packed is written and
     returned only with keep_cg; out is the same bit for bit either way.
     d must be 64.  w may be a RadialW."""
-    rw = w if isinstance(w, RadialW) else None
-    if rw is not None:
-        w = None
+    w, rw = _split_w(w)
     _chk_f32(h, w2, b2, w, base)
     E, d = h.shape[0], w2.shape[1]
     assert h.shape == (E, 2 * d) and w2.shape == (2, d, d)
     assert b2.numel() == 2 * d
     assert w is None or w.shape == (E, d)
     assert base is None or base.shape == (E, d)
-    half = E * d
     out = torch.empty(E, d, dtype=h.dtype, device=h.device)
     cg = torch.empty(2, E, d, dtype=h.dtype, device=h.device) \
         if keep_cg else None
+    head = (_fp(h), *_halves(w2), *_halves(b2))
+    rest = (_fp(base), *_halves(cg), _fp(out), E, d)
     if rw is not None:
         rw.check(E, d)
         _check(hip_lib().dm_gated_mlp_tail_fwd_fw_f32(
-            _fp(h), ctypes.cast(w2.data_ptr(), POINTER(c_float)),
-            ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
-            ctypes.cast(b2.data_ptr(), POINTER(c_float)),
-            ctypes.cast(b2.data_ptr() + 4 * d, POINTER(c_float)),
-            *rw.ptrs(), _fp(base) if base is not None else None,
-            ctypes.cast(cg.data_ptr(), POINTER(c_float)) if keep_cg else None,
-            ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float))
-            if keep_cg else None,
-            _fp(out), E, d, rw.bexp.shape[1], _stream()),
+            *head, *rw.ptrs(), *rest, rw.bexp.shape[1], _stream()),
             "dm_gated_mlp_tail_fwd_fw_f32")
-        return out, cg
-    _check(hip_lib().dm_gated_mlp_tail_fwd_f32(
-        _fp(h), ctypes.cast(w2.data_ptr(), POINTER(c_float)),
-        ctypes.cast(w2.data_ptr() + 4 * d * d, POINTER(c_float)),
-        ctypes.cast(b2.data_ptr(), POINTER(c_float)),
-        ctypes.cast(b2.data_ptr() + 4 * d, POINTER(c_float)),
-        _fp(w) if w is not None else None,
-        _fp(base) if base is not None else None,
-        ctypes.cast(cg.data_ptr(), POINTER(c_float)) if keep_cg else None,
-        ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float))
-        if keep_cg else None,
-        _fp(out), E, d, _stream()), "dm_gated_mlp_tail_fwd_f32")
+    else:
+        _check(hip_lib().dm_gated_mlp_tail_fwd_f32(
+            *head, _fp(w), *rest, _stream()), "dm_gated_mlp_tail_fwd_f32")
     return out, cg
-
-
-def use_fused_mlp_full() -> bool:
-    """Whole-MLP kernel switch: DM_NO_FUSED_MLP_FULL=1 restores the
-    first-layer + tail kernel pair everywhere, for A/B runs in one build."""
-    return os.environ.get("DM_NO_FUSED_MLP_FULL", "0") != "1"
 
 
 def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
@@ -912,9 +856,9 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
     None with want_out=False (keep only; w and base are then not read).
     Values are the two-kernel path's bit for bit.  w may be a RadialW (two
     tables, with out)."""
-    rw = w if isinstance(w, RadialW) and want_out else None
-    if isinstance(w, RadialW):
-        w = None
+    w, rw = _split_w(w)
+    if not want_out:
+        w = rw = base = None
     _chk_f32(row, wt, bias, *tables, w2, b2, w, base)
     E, d = row.shape[0], w2.shape[1]
     assert wt.shape == (d, 2 * d) and w2.shape == (2, d, d)
@@ -922,11 +866,8 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
     assert len(tables) == len(idx) and len(tables) in (2, 3)
     assert all(t.shape[1] == 2 * d for t in tables)
     assert keep or want_out
-    if not want_out:
-        w = base = None
     assert w is None or w.shape == (E, d)
     assert base is None or base.shape == (E, d)
-    half = E * d
     z = torch.empty(E, 2 * d, dtype=row.dtype, device=row.device) \
         if keep else None
     if E == 0:
@@ -936,33 +877,21 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
         if keep else None
     out = torch.empty(E, d, dtype=row.dtype, device=row.device) \
         if want_out else None
-
-    def at(t, off=0):
-        return ctypes.cast(t.data_ptr() + off, POINTER(c_float))
-    tail = (at(w2), at(w2, 4 * d * d), at(b2), at(b2, 4 * d),
-            _fp(w) if w is not None else None,
-            _fp(base) if base is not None else None,
-            _fp(z) if keep else None,
-            at(cg) if keep else None, at(cg, 4 * half) if keep else None,
-            _fp(out) if want_out else None, E, wt.shape[0], d, _stream())
+    first = (_fp(row), _fp(wt), _fp(bias), *map(_fp, tables),
+             *map(_ip, idx), *_halves(w2), *_halves(b2))
+    rest = (_fp(base), _fp(z), *_halves(cg), _fp(out), E, wt.shape[0], d)
     if rw is not None:
         assert len(tables) == 2, "a factored w takes the two-gather form"
         rw.check(E, d)
-        tail = tail[:4] + rw.ptrs() + tail[5:-1] + (rw.bexp.shape[1],
-                                                    _stream())
         _check(hip_lib().dm_gated_mlp3_fw_f32(
-            _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
-            _ip(idx[0]), _ip(idx[1]), *tail), "dm_gated_mlp3_fw_f32")
-        return z, cg, out
-    if len(tables) == 2:
-        _check(hip_lib().dm_gated_mlp3_f32(
-            _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
-            _ip(idx[0]), _ip(idx[1]), *tail), "dm_gated_mlp3_f32")
+            *first, *rw.ptrs(), *rest, rw.bexp.shape[1], _stream()),
+            "dm_gated_mlp3_fw_f32")
+    elif len(tables) == 2:
+        _check(hip_lib().dm_gated_mlp3_f32(*first, _fp(w), *rest, _stream()),
+               "dm_gated_mlp3_f32")
     else:
-        _check(hip_lib().dm_gated_mlp4_f32(
-            _fp(row), _fp(wt), _fp(bias), _fp(tables[0]), _fp(tables[1]),
-            _fp(tables[2]), _ip(idx[0]), _ip(idx[1]), _ip(idx[2]), *tail),
-            "dm_gated_mlp4_f32")
+        _check(hip_lib().dm_gated_mlp4_f32(*first, _fp(w), *rest, _stream()),
+               "dm_gated_mlp4_f32")
     return z, cg, out
 
 
@@ -979,8 +908,8 @@ class _GatedMlpTail(torch.autograd.Function):
     """Everything of a gated MLP after its first layer, as one node:
     out = base + silu(c) * sigmoid(g) * w with cg = baddbmm(b2, h halves,
     w2).  The forward is the single dm_gated_mlp_tail_fwd_f32 launch, which
-    writes cg for the backward and never reads it back (with
-    DM_NO_FUSED_MLP_FWD=1: the baddbmm and dm_gated_combine_fwd_f32 of
+    writes cg for the backward and never reads it back (where
+    mlp_path.fused_tail_fwd says no: baddbmm + raw_combine_fwd, as in
     chgnet._SecondLayer + _GatedCombinePacked); the backward is the single
     dm_gated_mlp_tail_bwd_f32 launch, which goes from go to dz without
     writing dcg or dh.
@@ -999,19 +928,11 @@ class _GatedMlpTail(torch.autograd.Function):
         d = w2.shape[1]
         assert z.shape == h.shape and z.shape[1] == 2 * d
         assert not w2.requires_grad and not b2.requires_grad
-        if d == 64 and use_fused_tail_fwd():
+        if mlp_path.fused_tail_fwd(HipOps, d):
             out, cg = raw_mlp_tail_fwd(h, w2, b2, w, base, True)
         else:
             cg = torch.baddbmm(b2, h.view(-1, 2, d).transpose(0, 1), w2)
-            half = cg.shape[1] * d
-            out = torch.empty(cg.shape[1], d, dtype=cg.dtype,
-                              device=cg.device)
-            _check(hip_lib().dm_gated_combine_fwd_f32(
-                ctypes.cast(cg.data_ptr(), POINTER(c_float)),
-                ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
-                _fp(w) if w is not None else None,
-                _fp(base) if base is not None else None, _fp(out), half,
-                _stream()), "dm_gated_combine_fwd_f32")
+            out = raw_combine_fwd(cg, w, base)
         ctx.save_for_backward(cg, z, w2, w)
         ctx.has_base = base is not None
         return out
@@ -1081,8 +1002,7 @@ class HipOps:
             "mlp_tail: z and h must be the outputs of one first-layer call"
         assert z.shape == h.shape and w2.shape[1] * 2 == z.shape[1]
         return _GatedMlpTail.apply(
-            z, h, w2, b2, w.contiguous() if w is not None else None,
-            base.contiguous() if base is not None else None)
+            z, h, w2, b2, _cont(w), _cont(base))
 
     def mlp_tail_act(self, h, w2, b2, w=None, base=None):
         """mlp_tail's value for passes that record nothing (torch.no_grad
@@ -1093,10 +1013,10 @@ class HipOps:
             t is not None and t.requires_grad for t in (h, w, base))), \
             "mlp_tail_act is the no-grad form; use mlp_tail"
         if not isinstance(w, RadialW):
-            w = w.contiguous() if w is not None else None
+            w = _cont(w)
         return raw_mlp_tail_fwd(
             h.contiguous(), w2, b2, w,
-            base.contiguous() if base is not None else None, False)[0]
+            _cont(base), False)[0]
 
     def scatter_edges(self, msg, pd, base=None):
         return _SegSum.apply(msg, pd.dst, pd.row_ptr, pd.n_atoms, base)
@@ -1111,44 +1031,13 @@ class HipOps:
     #    backward (distmlip_amd.conv); see ops_base docstring ------------
 
     def r_gather_add3(self, zs, zd, ze, pd):
-        _chk_f32(zs, zd, ze)
-        z = torch.empty_like(ze)
-        h = torch.empty_like(ze)
-        _check(hip_lib().dm_gather_add3_f32(
-            _fp(zs), _fp(zd), _fp(ze), _ip(pd.src), _ip(pd.dst), _fp(z),
-            _fp(h), ze.shape[0], ze.shape[1], _stream()),
-            "dm_gather_add3_f32")
-        return z, h
-
-    def _cg_ptrs(self, cg):
-        half = cg.shape[1] * cg.shape[2]
-        return (ctypes.cast(cg.data_ptr(), POINTER(c_float)),
-                ctypes.cast(cg.data_ptr() + 4 * half, POINTER(c_float)),
-                half)
+        return raw_gather_add3(zs, zd, ze, pd.src, pd.dst)
 
     def r_combine_fwd(self, cg, w, base):
-        _chk_f32(cg, w, base)
-        c_ptr, g_ptr, half = self._cg_ptrs(cg)
-        out = torch.empty(cg.shape[1], cg.shape[2], dtype=cg.dtype,
-                          device=cg.device)
-        _check(hip_lib().dm_gated_combine_fwd_f32(
-            c_ptr, g_ptr, _fp(w) if w is not None else None,
-            _fp(base) if base is not None else None, _fp(out), half,
-            _stream()), "dm_gated_combine_fwd_f32")
-        return out
+        return raw_combine_fwd(cg, w, base)
 
     def r_combine_bwd(self, go, cg, w):
-        _chk_f32(go, cg, w)
-        c_ptr, g_ptr, half = self._cg_ptrs(cg)
-        dcg = torch.empty_like(cg)
-        dc_ptr = ctypes.cast(dcg.data_ptr(), POINTER(c_float))
-        dg_ptr = ctypes.cast(dcg.data_ptr() + 4 * half, POINTER(c_float))
-        dw = torch.empty_like(w) if w is not None else None
-        _check(hip_lib().dm_gated_combine_bwd_f32(
-            _fp(go), c_ptr, g_ptr, _fp(w) if w is not None else None,
-            dc_ptr, dg_ptr, _fp(dw) if dw is not None else None, half,
-            _stream()), "dm_gated_combine_bwd_f32")
-        return dcg, dw
+        return raw_combine_bwd(go, cg, w)
 
     def r_silu_bwd(self, go_h, z):
         return raw_silu_bwd(go_h.contiguous(), None, z)
@@ -1163,15 +1052,7 @@ class HipOps:
         """(z, h) of the fused first layer with z stored: r_gather_add3
         over addmm(bias, erow, wt) without that [E,2d] transient (wt =
         the [64,128] fusedT pack only)."""
-        _chk_f32(erow, wt, bias, zs, zd)
-        E, dout = erow.shape[0], wt.shape[1]
-        z = torch.empty(E, dout, dtype=erow.dtype, device=erow.device)
-        h = torch.empty_like(z)
-        _check(hip_lib().dm_edge_mlp3_f32(
-            _fp(erow), _fp(wt), _fp(bias), _fp(zs), _fp(zd), _ip(pd.src),
-            _ip(pd.dst), _fp(z), _fp(h), E, wt.shape[0], dout, _stream()),
-            "dm_edge_mlp3_f32")
-        return z, h
+        return raw_edge_mlp3(erow, wt, bias, zs, zd, pd.src, pd.dst)
 
     def r_edge_mlp_bwd(self, dz, wt, gbase=None, out=None):
         """(gbase +) dz @ wt.t() in one kernel (wt = the [64,128] fusedT
@@ -1227,14 +1108,7 @@ class HipOps:
     # line-graph raw primitives (bond-conv hand-sequenced reverse)
 
     def r_gather_add4(self, z1, z2, za, zv, pd):
-        _chk_f32(z1, z2, za, zv)
-        z = torch.empty_like(za)
-        h = torch.empty_like(za)
-        _check(hip_lib().dm_gather_add4_f32(
-            _fp(z1), _fp(z2), _fp(za), _fp(zv), _ip(pd.l_src), _ip(pd.l_dst),
-            _ip(pd.center), _fp(z), _fp(h), za.shape[0], za.shape[1],
-            _stream()), "dm_gather_add4_f32")
-        return z, h
+        return raw_gather_add4(z1, z2, za, zv, pd)
 
     def r_gather_lsrc(self, x, pd):
         return raw_gather(x.contiguous(), pd.l_src)
@@ -1259,14 +1133,12 @@ class HipOps:
     def gated_combine(self, c, g, w=None, base=None):
         return _GatedCombine.apply(
             c.contiguous(), g.contiguous(),
-            w.contiguous() if w is not None else None,
-            base.contiguous() if base is not None else None)
+            _cont(w), _cont(base))
 
     def gated_combine_packed(self, cg, w=None, base=None):
         return _GatedCombinePacked.apply(
             cg.contiguous(),
-            w.contiguous() if w is not None else None,
-            base.contiguous() if base is not None else None)
+            _cont(w), _cont(base))
 
     def edge_geom_rbf(self, pos, offshift, freqs, cutoff, pexp, pd):
         return _EdgeGeomRbf.apply(pos.contiguous(), offshift.contiguous(),

@@ -53,8 +53,11 @@ the permutation CSRs the graph builder emits; `csr` is an optional
   RAW primitives (prefix r_): NON-differentiable single kernels used by
   the hand-sequenced conv backward (distmlip_amd.conv._AtomConvFn),
   which replaces autograd's per-tensor gradient accumulation for the
-  atom-conv blocks.  Both backends implement them so the CPU fp64
-  exactness tests cover the product's hand-written reverse pass:
+  atom-conv blocks.  Both backends implement the ones not marked OPTIONAL,
+  so the CPU fp64 exactness tests cover the product's hand-written reverse
+  pass.  The OPTIONAL ones exist on HipOps (d = 64, fp32);
+  distmlip_amd.mlp_path decides where each is used, and conv.py composes
+  the same value from the others where it is not:
 
     r_gather_add3(zs, zd, ze, pd)        -> (z, silu(z)) raw forward
     r_combine_fwd(cg, w, base)           -> base + silu(cg0)*sigmoid(cg1)*w
@@ -63,10 +66,8 @@ the permutation CSRs the graph builder emits; `csr` is an optional
     r_mlp_tail_bwd(go, cg, w, z, w2)     -> (dz, dw): r_combine_bwd, the
                                             second layer's reverse GEMMs
                                             and r_silu_bwd as one kernel.
-                                            OPTIONAL (HipOps, d = 64): conv
-                                            falls back to the three calls
-                                            where a backend lacks it.  A
-                                            backend with the class attribute
+                                            OPTIONAL.  A backend with the
+                                            class attribute
                                             tail_bwd_indexed = True also takes
                                             go_idx=int32 [E]: go is then a
                                             [N,d] table read as go[go_idx]
@@ -74,14 +75,11 @@ the permutation CSRs the graph builder emits; `csr` is an optional
     r_edge_mlp3(e, wt, bias, zs, zd, pd) -> (z, silu(z)) with z = e @ wt +
                                             bias + zs[src] + zd[dst]: the
                                             per-edge GEMM inside r_gather_add3.
-                                            OPTIONAL (HipOps, wt [64,128]):
-                                            conv falls back to addmm +
-                                            r_gather_add3
+                                            OPTIONAL (wt [64,128])
     r_edge_mlp_bwd(dz, wt, gbase, out)   -> (gbase +) dz @ wt.t(), its
                                             reverse with the gradient sum in
                                             the epilogue; out may be gbase.
-                                            OPTIONAL (HipOps, wt [64,128]):
-                                            conv falls back to addmm
+                                            OPTIONAL (wt [64,128])
     r_move_rows(src, si, dst, di, add=False)
                                          -> dst, written IN PLACE:
                                             dst[di[i]] (=|+=) src[si[i]] by
@@ -89,39 +87,32 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             are int64 [M] (pd.map_de /
                                             pd.map_ude) or None for the
                                             identity; di must be unique.
-                                            OPTIONAL (HipOps, fp32): conv's
-                                            edge_to_bond / bond_to_edge fall
-                                            back to torch index ops
+                                            OPTIONAL
     r_zero_rows(dst, di)                 -> dst with rows di zeroed IN PLACE.
                                             OPTIONAL, with r_move_rows
     r_mlp_tail_fwd(h, w2, b2, w, base)   -> (cg, out): the second layer's
                                             batched GEMM and r_combine_fwd as
-                                            one kernel.  OPTIONAL (HipOps,
-                                            d = 64): conv falls back to the
-                                            two calls where a backend lacks it
+                                            one kernel.  OPTIONAL
     r_gated_mlp3(e, wt, bias, zs, zd, pd, w2, b2, w, base, want_out=True)
                                          -> (z, cg, out): r_edge_mlp3 and
                                             r_mlp_tail_fwd as one kernel, same
                                             values bit for bit; with
                                             want_out=False out is None and w,
-                                            base are not read.  OPTIONAL
-                                            (HipOps, d = 64): conv falls back
-                                            to the two calls.  (The keep form
-                                            over three gathers exists as the C
-                                            entry dm_gated_mlp4_f32 only:
-                                            bond_fwd / angle_fwd run their
-                                            first layer through rocBLAS)
-    factored_w = True (class attribute)  -> OPTIONAL (HipOps, d = 64, n_rbf =
-                                            9): mlp_tail_act, r_mlp_tail_fwd,
-                                            r_gated_mlp3 and r_mlp_tail_bwd
-                                            take an ops.RadialW (bexp, W,
-                                            mask) as w and compute w = mask *
-                                            (bexp @ W.t()) in the kernel;
-                                            r_mlp_tail_bwd then returns (dz,
-                                            dbexp), added onto the RadialW's
-                                            dbexp_acc in place when given.
-                                            conv builds the dense w where a
-                                            backend lacks it
+                                            base are not read.  OPTIONAL.  (The
+                                            keep form over three gathers
+                                            exists as the C entry
+                                            dm_gated_mlp4_f32 only: bond_fwd /
+                                            angle_fwd run their first layer
+                                            through rocBLAS)
+    factored_w = True (class attribute)  -> OPTIONAL (n_rbf = 9): mlp_tail_act,
+                                            r_mlp_tail_fwd, r_gated_mlp3 and
+                                            r_mlp_tail_bwd take an ops.RadialW
+                                            (bexp, W, mask) as w and compute
+                                            w = mask * (bexp @ W.t()) in the
+                                            kernel; r_mlp_tail_bwd then returns
+                                            (dz, dbexp), added onto the
+                                            RadialW's dbexp_acc in place when
+                                            given
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

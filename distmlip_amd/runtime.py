@@ -32,10 +32,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from distmlip_amd import mlp_path
 from distmlip_amd.conv import (_AtomBlockFn, _AtomBlockKeepFn, _AtomConvFn,
                                _BondConvFn, atom_block_available,
-                               bond_to_edge, conv_fn_available, edge_to_bond,
-                               final_keep_enabled, row_exchange_enabled)
+                               bond_to_edge, conv_fn_available, edge_to_bond)
 from distmlip_amd.chgnet import (
     PartitionData,
     _packed_weights,
@@ -444,8 +444,7 @@ class SpmdEngine:
         # unchecked op-by-op path keeps the out-of-place torch lines, since
         # there an in-place write could meet a saved tensor
         # (nor does the whole-graph Function, which does its own exchange)
-        row_x = (ckpt and use_bg and row_exchange_enabled()
-                 and _os.environ.get("DM_WHOLE_GRAPH_CKPT") != "1")
+        row_x = ckpt and use_bg and mlp_path.row_exchange()
         if use_bg:
             # owned bond geometry from local edges; ghosts by one halo each
             # (reference chgnet.py:129-164).  map_ude is a permutation of
@@ -538,7 +537,7 @@ class SpmdEngine:
                     # the final block's backward follows its forward at
                     # once: it keeps its saves instead of recomputing them
                     fn = _AtomBlockKeepFn if (
-                        layer_i == -1 and final_keep_enabled()) \
+                        layer_i == -1 and mlp_path.final_keep()) \
                         else _AtomBlockFn
                     return fn.apply(
                         v, e, bond_expansion, wbb_w, wab_w, edge_mask, pd,
@@ -555,9 +554,8 @@ class SpmdEngine:
         # 140.5 ms/step); the streamed-recompute mode LOSES at si1m
         # (2486 vs 2081 ms — the lean re-runs outweigh the saved adds), so
         # checkpointed steps stay on the op-by-op path unless forced
-        wg_ckpt_ok = _os.environ.get("DM_WHOLE_GRAPH_CKPT") == "1"
         if (P == 1 and not mask_cutoffs and d % 2 == 0
-                and (not ckpt or wg_ckpt_ok)
+                and (not ckpt or mlp_path.whole_graph_ckpt())
                 and whole_graph_available(
                     ops, _packed_weights(core.atom_convs[0].edge_mlp))):
             wbb_m = w_bb if w_bb is not None else \
@@ -603,8 +601,8 @@ class SpmdEngine:
                     w3 = w_3b if w_3b is not None else \
                         _m(core.threebody_bond_weights(e3), bond_mask)
                     pb = _packed_weights(_blk.bond_mlp)
-                    if (d % 2 == 0 and conv_fn_available(ops, pb)
-                            and hasattr(ops, "r_gather_add4")):
+                    if d % 2 == 0 and conv_fn_available(ops, pb,
+                                                        "r_gather_add4"):
                         mask_l = None
                         if bond_mask is not None:
                             mask_l = ops.r_gather_ldst(
