@@ -52,7 +52,8 @@ def _second_bwd(dcg, w2, d):
 def _mlp_tail_bwd(ops, go, cg, w, z, w2, d):
     """(dz, dw) from the gradient go of r_combine_fwd(cg, w, base): one
     kernel where mlp_path allows r_mlp_tail_bwd, else combine reverse +
-    second-layer GEMMs + silu reverse."""
+    second-layer GEMMs + silu reverse.  (dz, dbexp, seg_dst(dz)) for a
+    factored w that carries the graph."""
     if mlp_path.fused_tail_bwd(ops, d):
         return ops.r_mlp_tail_bwd(go, cg, w, z, w2)
     dcg, dw = ops.r_combine_bwd(go, cg, w)
@@ -181,14 +182,17 @@ def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d,
     return v2, e2, (z1, cg1, z2, cg2)
 
 
-def _node_grad(ops, pd, go_v2, dzs, weights):
+def _node_grad(ops, pd, go_v2, dzs, weights, sds=None):
     """go_v2 + sum over the MLPs of seg_src(dz) @ ws + seg_dst(dz) @ wd: the
     v gradient of an atom conv, every term a fused addmm.  dzs (one dz per
     (ws, wd) of weights, None to skip) is emptied as it goes, so each dz is
-    freed once consumed when the caller holds no other reference."""
+    freed once consumed when the caller holds no other reference.  sds: per
+    MLP, the list of what its reverse tail returned after (dz, dw): empty, or
+    seg_dst(dz) from that kernel's epilogue, used in place of r_seg_dst."""
     gv = go_v2
-    for ws, wd in weights:
+    for i, (ws, wd) in enumerate(weights):
         dz = dzs.pop(0)
+        sd = sds[i] if sds else ()
         if dz is None:
             continue
         if gv is None:
@@ -197,7 +201,7 @@ def _node_grad(ops, pd, go_v2, dzs, weights):
             gv = torch.addmm(go_v2, ops.r_seg_src(dz, pd), ws)
         else:
             gv.addmm_(ops.r_seg_src(dz, pd), ws)
-        gv.addmm_(ops.r_seg_dst(dz, pd), wd)
+        gv.addmm_(sd[0] if sd else ops.r_seg_dst(dz, pd), wd)
         del dz
     return gv
 
@@ -229,15 +233,20 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     ft2 = _fused_first_bwd(ops, packs_node, d)
     go_v2 = go_v2.contiguous() if go_v2 is not None else None
     go_e2 = go_e2.contiguous() if go_e2 is not None else None
+    # factored weights that carry the graph: each reverse tail then returns
+    # seg_dst(dz) as a third result, for _node_grad (sd1, sd2: [] without)
+    if factored and need_gv and mlp_path.fused_seg(ops, d):
+        wbb, wab = wbb.with_seg(pd), wab.with_seg(pd)
 
     # node MLP reverse (v2 = v + seg_dst(msg))
+    sd2 = []
     if go_v2 is not None:
         if ft2 is not None and mlp_path.indexed_tail_bwd(ops, d):
-            dz2, dwab = ops.r_mlp_tail_bwd(go_v2, cg2, wab, z2, w22,
-                                           pd.dst)     # go_idx
+            dz2, dwab, *sd2 = ops.r_mlp_tail_bwd(go_v2, cg2, wab, z2, w22,
+                                                 pd.dst)     # go_idx
         else:
             dmsg = ops.r_gather_dst(go_v2, pd)
-            dz2, dwab = _mlp_tail_bwd(ops, dmsg, cg2, wab, z2, w22, d)
+            dz2, dwab, *sd2 = _mlp_tail_bwd(ops, dmsg, cg2, wab, z2, w22, d)
             del dmsg
         del z2, cg2
         # e2 grad: external + the node MLP's per-edge GEMM, fused.  The
@@ -260,7 +269,7 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     if factored and dwab is not None:
         wbb = wbb.with_acc(dwab)
         dwab = None
-    dz1, dwbb = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
+    dz1, dwbb, *sd1 = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
     del z1, cg1
     # base passthrough + GEMM; in place only over the ge2 made above
     if ft1 is not None:
@@ -272,8 +281,8 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     dzs = [dz1, dz2]
     del dz1, dz2
     # v grad: passthrough + all four per-node GEMM backs, fused
-    gv = _node_grad(ops, pd, go_v2, dzs, ((ws1, wd1), (ws2, wd2))) \
-        if need_gv else None
+    gv = _node_grad(ops, pd, go_v2, dzs, ((ws1, wd1), (ws2, wd2)),
+                    (sd1, sd2)) if need_gv else None
     if acc_wbb is not None:
         acc_wbb.add_(dwbb)
         dwbb = None

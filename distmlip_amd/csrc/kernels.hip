@@ -968,6 +968,10 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 //        work (18 fma per column and row beside 2 sigmoids; as MFMAs they
 //        would be a K = 9 product and a 32-step chain on a fifth
 //        accumulator, 64 more registers)
+//   (the body is gated_mlp_tail_bwd_body, shared with the SEG kernel below;
+//   since then <2> takes 214 VGPR, the dense forms 153 / 148 as before it)
+//   k_gated_mlp_tail_bwd_seg (seg_tile_sums in the epilogue, no packed fp32
+//   forms): <1> 158 VGPR, <2> 160, 0 AGPR, no scratch, 3 waves/SIMD
 // Indexed form (IDX, dm_gated_mlp_tail_bwd_idx_f32): go is a [N,64] table
 // and row r reads table row idx[r], one int32 index per lane per tile, loaded
 // inside the live predicate.  This is the reverse of a segment sum feeding
@@ -996,9 +1000,12 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 // ---------------------------------------------------------------------------
 constexpr int TAIL_CHUNK = 4;    // row slices (of 8) per load batch
 
-template <bool FULL>
+// KEEP_DZ: the dz values stored also replace their accumulators (acc is
+// then not const), for seg_tile_sums below.
+template <bool FULL, bool KEEP_DZ = false>
 __device__ __forceinline__ void mlp_tail_epilogue(
-        const f32x16 (&acc)[4], const float* __restrict__ z,
+        std::conditional_t<KEEP_DZ, f32x16, const f32x16> (&acc)[4],
+        const float* __restrict__ z,
         float* __restrict__ dz, int64_t base, int64_t E, int c, int h) {
     constexpr int G = 8;
 #pragma unroll
@@ -1028,7 +1035,9 @@ __device__ __forceinline__ void mlp_tail_epilogue(
                 for (int cb = 0; cb < 4; ++cb) {
                     const float x = zv[t][cb];
                     const float s = s4[cb];
-                    dp[32 * cb] = acc[cb][r] * (s * (1.0f + x * (1.0f - s)));
+                    const float v = acc[cb][r] * (s * (1.0f + x * (1.0f - s)));
+                    dp[32 * cb] = v;
+                    if constexpr (KEEP_DZ) acc[cb][r] = v;
                 }
             }
             __builtin_amdgcn_sched_barrier(0);   // one row at a time
@@ -1186,9 +1195,121 @@ __device__ __forceinline__ void mlp_tail_a_phase(
 #define DM_FW_BWD_WAVES 2
 #endif
 
-template <int HAS_W, bool IDX>
-__global__ __launch_bounds__(256, HAS_W == 2 ? DM_FW_BWD_WAVES : 3)
-void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
+// ---------------------------------------------------------------------------
+// Segment sums of dz over the dst-sorted rows, from the accumulators: what
+// dm_seg_sum_f32(dz, row_ptr) computes, without reading dz back (23.5 GB at
+// 46M rows).  seg[r] is the segment (node) of row r, non-decreasing.
+//  * A wave holds its tile's dz in the accumulator layout, the rows of a
+//    column split between the two half-waves in groups of four.  One
+//    v_permlane32_swap per register pair (acc[p], acc[p+2]) gives every lane
+//    all 32 rows of two columns: half h takes columns c + 64h and c + 32 + 64h.
+//  * The segment ids are wave-uniform: lane j holds row j's, read back with
+//    v_readlane, so the walk over the rows branches on scalars only.  Each
+//    lane adds its two columns in row order into fp64, the order of
+//    k_seg_sum_v4_u4.
+//  * A segment that is neither the tile's first nor its last is complete:
+//    rounded once to fp32 and stored to sums[node].  The first segment goes
+//    to part[tile][0], the last (if it is another) to part[tile][1], as fp64
+//    sums from 0, whether or not they continue in a neighbour tile;
+//    k_seg_fixup adds the pieces of each such node in tile order, and writes
+//    the nodes without rows.  A node within one tile therefore gets the bits
+//    of k_seg_sum_v4_u4, a node over several tiles a reassociated fp64 sum.
+// Plain stores only: each element of sums and part has one writer.
+// ---------------------------------------------------------------------------
+template <bool FULL>
+__device__ __forceinline__ void seg_tile_sums(
+        const f32x16 (&acc)[4], const int32_t* __restrict__ seg,
+        float* __restrict__ sums, double* __restrict__ part, int64_t tile,
+        int64_t E, int lane) {
+    const int64_t base = tile << 5;
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t r = base + c;
+    const int sv = seg[(FULL || r < E) ? r : E - 1];
+    // live rows of the tile; the same in every lane, made a scalar
+    const int n = FULL ? 32
+                       : __builtin_amdgcn_readfirstlane((int)(E - base));
+    float lo[2][16], hi[2][16];   // rows of half 0 / half 1, columns p
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const auto x = __builtin_amdgcn_permlane32_swap(
+                __float_as_uint(acc[p][q]), __float_as_uint(acc[p + 2][q]),
+                false, false);
+            lo[p][q] = __uint_as_float(x[0]);
+            hi[p][q] = __uint_as_float(x[1]);
+        }
+    const int col = c + 64 * h;
+    double a0 = 0.0, a1 = 0.0;
+    int cur = __builtin_amdgcn_readlane(sv, 0);
+    bool first = true;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        // (no break: the loop has to unroll, the rows are registers)
+        if (!FULL && j >= n) continue;
+        const int s = __builtin_amdgcn_readlane(sv, j);
+        if (j > 0 && s != cur) {
+            if (first) {
+                double* pp = part + (tile * 2) * 128 + col;
+                pp[0] = a0;
+                pp[32] = a1;
+            } else {
+                float* sp = sums + (int64_t)cur * 128 + col;
+                sp[0] = (float)a0;
+                sp[32] = (float)a1;
+            }
+            first = false;
+            cur = s;
+            a0 = a1 = 0.0;
+        }
+        // row j = (q & 3) + 8 * (q >> 2) + 4 * half
+        const int q = (j & 3) + 4 * (j >> 3);
+        a0 += (double)(((j >> 2) & 1) ? hi[0][q] : lo[0][q]);
+        a1 += (double)(((j >> 2) & 1) ? hi[1][q] : lo[1][q]);
+    }
+    double* pp = part + (tile * 2 + (first ? 0 : 1)) * 128 + col;
+    pp[0] = a0;
+    pp[32] = a1;
+}
+
+// One 32-lane group per node, a lane four columns: the node's pieces in
+// part, in tile order, from 0 in fp64, rounded once.  In tile t the node is
+// the first segment (slot 0) when it owns row 32t, else the last (slot 1)
+// when it owns the tile's last row, else seg_tile_sums has written it.
+__global__ void k_seg_fixup(const double* __restrict__ part,
+                            const int32_t* __restrict__ rp,
+                            float4* __restrict__ sums, int64_t N, int64_t E) {
+    const int lane = threadIdx.x & 31;
+    const int group = threadIdx.x >> 5;
+    const int groups_per_block = blockDim.x >> 5;
+    for (int64_t node = blockIdx.x * (int64_t)groups_per_block + group;
+         node < N; node += (int64_t)gridDim.x * groups_per_block) {
+        const int64_t lo = rp[node], hi = rp[node + 1];
+        double ax = 0, ay = 0, az = 0, aw = 0;
+        bool mine = lo == hi;
+        for (int64_t t = lo >> 5; lo < hi && t <= ((hi - 1) >> 5); ++t) {
+            const int64_t t0 = t << 5;
+            const int64_t tl = t0 + 31 < E ? t0 + 31 : E - 1;
+            int slot;
+            if (lo <= t0) slot = 0;
+            else if (hi - 1 >= tl) slot = 1;
+            else break;
+            const double2* pp =
+                (const double2*)(part + (t * 2 + slot) * 128 + 4 * lane);
+            const double2 u = pp[0], v = pp[1];
+            ax += u.x; ay += u.y; az += v.x; aw += v.y;
+            mine = true;
+        }
+        if (mine)
+            sums[node * 32 + lane] = make_float4((float)ax, (float)ay,
+                                                 (float)az, (float)aw);
+    }
+}
+
+// The reverse tail's body; SEG adds seg_tile_sums over dz (seg, sums, part).
+template <int HAS_W, bool IDX, bool SEG>
+__device__ __forceinline__
+void gated_mlp_tail_bwd_body(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
                           const int32_t* __restrict__ idx, // [E], IDX only
                           const float* __restrict__ cp,   // [E,64]
                           const float* __restrict__ gp,   // [E,64]
@@ -1204,8 +1325,12 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
                           const float* __restrict__ fwW,  // [64,9]
                           const float* __restrict__ fwmask,  // [E] or null
                           const float* dbexp_in,          // [E,9] or null
-                          float* dbexp) {                 // [E,9], may be
+                          float* dbexp,                   // [E,9], may be
                                                           // dbexp_in
+                          // SEG only
+                          const int32_t* __restrict__ seg,   // [E]
+                          float* __restrict__ sums,          // [N,128]
+                          double* __restrict__ part) {  // [tiles,2,128]
     __shared__ float4 wlds[64 * 32];
     __shared__ float4 wl9[HAS_W == 2 ? 64 * RBF_PAD / 4 : 1];
     if (HAS_W == 2) radial_stage_W((float*)wl9, fwW);
@@ -1298,11 +1423,65 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        if (base + 32 <= E)
-            mlp_tail_epilogue<true>(acc, z, dz, base, E, c, h);
-        else
-            mlp_tail_epilogue<false>(acc, z, dz, base, E, c, h);
+        if (base + 32 <= E) {
+            mlp_tail_epilogue<true, SEG>(acc, z, dz, base, E, c, h);
+            if (SEG) seg_tile_sums<true>(acc, seg, sums, part, tile, E, lane_t);
+        } else {
+            mlp_tail_epilogue<false, SEG>(acc, z, dz, base, E, c, h);
+            if (SEG) seg_tile_sums<false>(acc, seg, sums, part, tile, E, lane_t);
+        }
     }
+}
+
+template <int HAS_W, bool IDX>
+__global__ __launch_bounds__(256, HAS_W == 2 ? DM_FW_BWD_WAVES : 3)
+void k_gated_mlp_tail_bwd(const float* __restrict__ go,
+                          const int32_t* __restrict__ idx,
+                          const float* __restrict__ cp,
+                          const float* __restrict__ gp,
+                          const float* __restrict__ wp,
+                          const float* __restrict__ z,
+                          const float* __restrict__ w2c,
+                          const float* __restrict__ w2g,
+                          float* __restrict__ dz, float* __restrict__ dw,
+                          int64_t E, const float* __restrict__ fwW,
+                          const float* __restrict__ fwmask,
+                          const float* dbexp_in, float* dbexp) {
+    gated_mlp_tail_bwd_body<HAS_W, IDX, false>(
+        go, idx, cp, gp, wp, z, w2c, w2g, dz, dw, E, fwW, fwmask, dbexp_in,
+        dbexp, nullptr, nullptr, nullptr);
+}
+
+// The SEG form is a kernel of its own so that it alone is compiled without
+// the packed fp32 VALU forms, as s2act.hip is (the attribute is a device-side
+// one; the host pass would only warn that it ignores it).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DM_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DM_NO_PK_F32
+#endif
+
+template <int HAS_W, bool IDX>
+__global__ __launch_bounds__(256, HAS_W == 2 ? DM_FW_BWD_WAVES : 3)
+DM_NO_PK_F32
+void k_gated_mlp_tail_bwd_seg(const float* __restrict__ go,
+                              const int32_t* __restrict__ idx,
+                              const float* __restrict__ cp,
+                              const float* __restrict__ gp,
+                              const float* __restrict__ wp,
+                              const float* __restrict__ z,
+                              const float* __restrict__ w2c,
+                              const float* __restrict__ w2g,
+                              float* __restrict__ dz, float* __restrict__ dw,
+                              int64_t E, const float* __restrict__ fwW,
+                              const float* __restrict__ fwmask,
+                              const float* dbexp_in, float* dbexp,
+                              const int32_t* __restrict__ seg,
+                              float* __restrict__ sums,
+                              double* __restrict__ part) {
+    gated_mlp_tail_bwd_body<HAS_W, IDX, true>(
+        go, idx, cp, gp, wp, z, w2c, w2g, dz, dw, E, fwW, fwmask, dbexp_in,
+        dbexp, seg, sums, part);
 }
 
 // ---------------------------------------------------------------------------
@@ -3030,6 +3209,51 @@ int dm_gated_mlp_tail_bwd_fw_f32(const float* go, const int32_t* idx,
             go, nullptr, c, g, bexp, z, w2c, w2g, dz, nullptr, E, W, mask,
             dbexp_in, dbexp);
     DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp_tail_bwd_seg_f32(const float* go, const int32_t* idx,
+                                  const float* c, const float* g,
+                                  const float* w, const float* bexp,
+                                  const float* W, const float* mask,
+                                  const float* z, const float* w2c,
+                                  const float* w2g, float* dz, float* dw,
+                                  const float* dbexp_in, float* dbexp,
+                                  const int32_t* seg, const int32_t* row_ptr,
+                                  float* sums, double* part, int64_t E,
+                                  int64_t N, int64_t d, int64_t n_rbf,
+                                  uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64 || (bexp && n_rbf != N_RBF)) {
+        g_err = "gated_mlp_tail_bwd_seg is compiled for d=64, n_rbf=9";
+        return -1;
+    }
+    if (bexp ? (!W || !dbexp || w || dw) : (!w || !dw)) {
+        g_err = "gated_mlp_tail_bwd_seg: give w and dw, or bexp, W and dbexp";
+        return -1;
+    }
+    if (!seg || !row_ptr || !sums || !part) {
+        g_err = "gated_mlp_tail_bwd_seg: seg, row_ptr, sums and part must be "
+                "given";
+        return -1;
+    }
+    if (E > 0) {
+#define DM_TAIL_SEG(HW, IX, GRID, WP)                                         \
+        k_gated_mlp_tail_bwd_seg<HW, IX><<<GRID, BLOCK, 0, s>>>(              \
+            go, idx, c, g, WP, z, w2c, w2g, dz, dw, E, W, mask, dbexp_in,     \
+            dbexp, seg, sums, part)
+        if (bexp && idx) DM_TAIL_SEG(2, true, mlp_tail_bwd_fw_blocks(E), bexp);
+        else if (bexp) DM_TAIL_SEG(2, false, mlp_tail_bwd_fw_blocks(E), bexp);
+        else if (idx) DM_TAIL_SEG(1, true, edge_mlp_blocks(E), w);
+        else DM_TAIL_SEG(1, false, edge_mlp_blocks(E), w);
+#undef DM_TAIL_SEG
+        DM_CHECK_LAUNCH();
+    }
+    if (N > 0) {
+        k_seg_fixup<<<nblocks(N, BLOCK / 32), BLOCK, 0, s>>>(
+            part, row_ptr, (float4*)sums, N, E);
+        DM_CHECK_LAUNCH();
+    }
     return 0;
 }
 

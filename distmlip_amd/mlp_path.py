@@ -123,6 +123,19 @@ def factored_w(ops, d) -> bool:
             and fused_tail_fwd(ops, d) and fused_tail_bwd(ops, d))
 
 
+# DM_NO_FUSED_SEG=1: atom_bwd takes the dst segment sums of dz from
+# r_seg_dst launches instead of the reverse tails' epilogues.  Read at call
+# time like SWITCHES; it turns no other predicate off.
+NO_FUSED_SEG = "DM_NO_FUSED_SEG"
+
+
+def fused_seg(ops, d) -> bool:
+    """r_mlp_tail_bwd also returns r_seg_dst(dz) for a factored w that
+    carries the graph (RadialW.with_seg)."""
+    return (getattr(ops, "tail_bwd_seg", False) and factored_w(ops, d)
+            and os.environ.get(NO_FUSED_SEG, "0") != "1")
+
+
 # -- conv blocks and whole steps ---------------------------------------------
 
 def fused_keep_packs() -> bool:

@@ -95,6 +95,12 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_gated_mlp_tail_bwd_fw_f32.argtypes = [
             fp, ip, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, c_int64,
             c_int64, c_int64, c_uint64]
+        # the reverse tail with the dst segment sums of dz in its epilogue
+        lib.dm_gated_mlp_tail_bwd_seg_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_bwd_seg_f32.argtypes = [
+            fp, ip, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, ip,
+            ip, fp, POINTER(ctypes.c_double), c_int64, c_int64, c_int64,
+            c_int64, c_uint64]
         lib.dm_mace_tp_fwd_f32.restype = c_int32
         lib.dm_mace_tp_fwd_f32.argtypes = [fp, fp, fp, fp, ip, fp, c_int32,
                                            fp, fp, fp, fp, c_int64, c_int32,
@@ -745,20 +751,26 @@ class RadialW:
     kernels compute w where they use it (one fixed fp32 order, the same bits
     in all of them) and the dense array never exists.  r_mlp_tail_bwd then
     returns (dz, dbexp) instead of (dz, dw), with dbexp = (dw * mask) @ W
-    added onto dbexp_acc in place when that is given."""
+    added onto dbexp_acc in place when that is given.  With seg (a graph
+    whose dst-sorted rows are the tail's: with_seg) r_mlp_tail_bwd returns
+    (dz, dbexp, r_seg_dst(dz, seg)), the sums from the kernel's epilogue."""
 
-    __slots__ = ("bexp", "W", "mask", "dbexp_acc")
+    __slots__ = ("bexp", "W", "mask", "dbexp_acc", "seg")
 
-    def __init__(self, bexp, W, mask=None, dbexp_acc=None):
+    def __init__(self, bexp, W, mask=None, dbexp_acc=None, seg=None):
         self.bexp, self.W, self.dbexp_acc = bexp, W, dbexp_acc
         self.mask = mask.reshape(-1) if mask is not None else None
+        self.seg = seg
 
     @property
     def requires_grad(self):
         return self.bexp.requires_grad
 
     def with_acc(self, dbexp_acc):
-        return RadialW(self.bexp, self.W, self.mask, dbexp_acc)
+        return RadialW(self.bexp, self.W, self.mask, dbexp_acc, self.seg)
+
+    def with_seg(self, pd):
+        return RadialW(self.bexp, self.W, self.mask, self.dbexp_acc, pd)
 
     def check(self, E, d):
         _chk_f32(self.bexp, self.W, self.mask, self.dbexp_acc)
@@ -777,15 +789,23 @@ def _split_w(w):
     return (None, w) if isinstance(w, RadialW) else (w, None)
 
 
-def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None):
+def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None):
     """(dz, dw) of one gated MLP's tail in ONE kernel: the reverse of
     out = base + silu(cg[0]) * sigmoid(cg[1]) * w with cg = the second layer
     over silu(z).  go [E,d], cg [2,E,d] packed, w [E,d] or None, z [E,2d],
     w2 [2,d,d] (input x output per half).  d must be 64.  With go_idx
     (int32 [E]) go is a [N,d] table and row r takes go[go_idx[r]]: the
     result on the materialized go[go_idx], without that gather.
-    w may be a RadialW: (dz, dbexp) is returned then."""
+    w may be a RadialW: (dz, dbexp) is returned then.
+    seg (a graph with dst int32 [E] sorted, row_ptr int32 [N+1] and n_atoms;
+    a RadialW brings its own) adds raw_seg_sum(dz, seg.row_ptr, N) as a third
+    result, summed in the kernel's epilogue from the registers that hold dz
+    and finished by a pass over per-tile fp64 partials: the bits of
+    raw_seg_sum for a node whose rows lie within one 32-row tile, at most
+    1 ulp off for a node spread over several.  It needs a w."""
     w, rw = _split_w(w)
+    if rw is not None and seg is None:
+        seg = rw.seg
     _chk_f32(go, cg, w, z, w2)
     d = go.shape[1]
     E = go.shape[0] if go_idx is None else go_idx.shape[0]
@@ -796,6 +816,29 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None):
             and go_idx.device == go.device
     dz = torch.empty_like(z)
     lib = hip_lib()
+    if seg is not None:
+        assert seg.dst.shape == (E,) and seg.dst.dtype == torch.int32 \
+            and seg.row_ptr.dtype == torch.int32 \
+            and seg.row_ptr.shape == (seg.n_atoms + 1,)
+        acc = dw = dbexp = None
+        if rw is not None:
+            rw.check(E, d)
+            acc = rw.dbexp_acc
+            dbexp = acc if acc is not None else torch.empty_like(rw.bexp)
+        else:
+            dw = torch.empty_like(w)
+        sums = torch.empty(seg.n_atoms, 2 * d, dtype=z.dtype, device=z.device)
+        part = torch.empty((E + 31) // 32, 2, 2 * d, dtype=torch.float64,
+                           device=z.device)
+        _check(lib.dm_gated_mlp_tail_bwd_seg_f32(
+            _fp(go), _ip(go_idx), *_halves(cg), _fp(w),
+            *(rw.ptrs() if rw is not None else (None, None, None)), _fp(z),
+            *_halves(w2), _fp(dz), _fp(dw), _fp(acc), _fp(dbexp),
+            _ip(seg.dst), _ip(seg.row_ptr), _fp(sums),
+            ctypes.cast(part.data_ptr(), POINTER(ctypes.c_double)), E,
+            seg.n_atoms, d, rw.bexp.shape[1] if rw is not None else 0,
+            _stream()), "dm_gated_mlp_tail_bwd_seg_f32")
+        return dz, (dbexp if rw is not None else dw), sums
     if rw is not None:
         rw.check(E, d)
         acc = rw.dbexp_acc
@@ -951,6 +994,7 @@ class HipOps:
     is_reference = False
     tail_bwd_indexed = True      # r_mlp_tail_bwd takes go_idx
     factored_w = True            # the w of the MLP tails may be a RadialW
+    tail_bwd_seg = True          # ... and may carry a graph (with_seg)
 
     def gather(self, x, idx, csr=None):
         if csr is None:
@@ -1045,7 +1089,8 @@ class HipOps:
     def r_mlp_tail_bwd(self, go, cg, w, z, w2, go_idx=None):
         """(dz, dw): r_combine_bwd + second-layer reverse + r_silu_bwd in
         one kernel (d = 64 only).  go_idx: go is a node table read by index
-        (r_gather_dst folded in).  With w a RadialW: (dz, dbexp)."""
+        (r_gather_dst folded in).  With w a RadialW: (dz, dbexp), and with
+        one that carries a graph (with_seg): (dz, dbexp, r_seg_dst(dz))."""
         return raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx)
 
     def r_edge_mlp3(self, erow, wt, bias, zs, zd, pd):

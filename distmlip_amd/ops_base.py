@@ -113,6 +113,12 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             (dz, dbexp), added onto the
                                             RadialW's dbexp_acc in place when
                                             given
+    tail_bwd_seg = True (class attribute) -> OPTIONAL, with factored_w: for a
+                                            RadialW.with_seg(pd),
+                                            r_mlp_tail_bwd returns (dz, dbexp,
+                                            r_seg_dst(dz, pd)), the sums from
+                                            the kernel's epilogue (at most
+                                            1 ulp from r_seg_dst's)
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

@@ -259,6 +259,34 @@ int dm_gated_mlp_tail_bwd_fw_f32(const float* go, const int32_t* idx,
                                  float* dbexp, int64_t E, int64_t d,
                                  int64_t n_rbf, uint64_t stream);
 
+/* The reverse tail with the dst segment sums of dz folded in: one entry for
+ * dm_gated_mlp_tail_bwd_f32 / _idx_f32 (w and dw given, bexp NULL; idx NULL
+ * for the plain form) and dm_gated_mlp_tail_bwd_fw_f32 (bexp, W and dbexp
+ * given, w and dw NULL), followed by
+ *   dm_seg_sum_f32(dz, row_ptr, NULL, sums, N, 2d)
+ * without dz being read back.  dz, dw and dbexp are those entries' bit for
+ * bit.  seg [E] int32 is the segment of each row, non-decreasing and in
+ * [0,N), with row_ptr [N+1] its CSR form (rows row_ptr[n] .. row_ptr[n+1]-1
+ * have seg == n); sums is [N,2d] fp32.  part is a workspace of
+ * 2 * ceil(E/32) * 2d doubles.  A node whose rows lie within one tile of 32
+ * rows (row >> 5) gets the bits of dm_seg_sum_f32; a node spread over
+ * several tiles gets the fp64 sum of its per-tile fp64 sums, in tile order,
+ * rounded once to fp32 (at most 1 ulp from dm_seg_sum_f32, nearly always
+ * equal).  Nodes without rows get 0.  No atomics: the result is
+ * deterministic.  Two launches: the tail kernel and a pass over part.
+ * Compiled for d = 64, n_rbf = 9; the form without w is not built. */
+int dm_gated_mlp_tail_bwd_seg_f32(const float* go, const int32_t* idx,
+                                  const float* c, const float* g,
+                                  const float* w, const float* bexp,
+                                  const float* W, const float* mask,
+                                  const float* z, const float* w2c,
+                                  const float* w2g, float* dz, float* dw,
+                                  const float* dbexp_in, float* dbexp,
+                                  const int32_t* seg, const int32_t* row_ptr,
+                                  float* sums, double* part, int64_t E,
+                                  int64_t N, int64_t d, int64_t n_rbf,
+                                  uint64_t stream);
+
 /* Fused edge geometry + radial basis (replaces the torch chain for
  * chgnet.py:96-124): per local edge e,
  *   bv[e]  = pos[dst[e]] + offshift[e] - pos[src[e]]
