@@ -207,7 +207,8 @@ def _node_grad(ops, pd, go_v2, dzs, weights, sds=None):
 
 
 def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
-             go_v2, go_e2, acc_wbb=None, acc_wab=None, need_gv=True):
+             go_v2, go_e2, acc_wbb=None, acc_wab=None, need_gv=True,
+             patch=None):
     """Hand-sequenced reverse of atom_fwd.  Returns (gv, ge, dwbb, dwab), or
     with factored wbb / wab (ops.RadialW) (gv, ge, dbexp, None), dbexp being
     the gradient of their common bexp through both weights;
@@ -221,7 +222,12 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     node MLP's tail reads go_v2 by pd.dst instead of a gathered copy.
     saved may be a list: it is emptied, so each save is freed as soon as
     it is consumed.  need_gv=False skips the four segment sums and GEMMs
-    of the v gradient (gv is None) when v takes no gradient."""
+    of the v gradient (gv is None) when v takes no gradient.
+
+    patch ([B,d], from an ExchangeHolder): the rows pd.map_de of go_e2 are
+    stale and stand for patch[pd.map_ude].  The node MLP's r_edge_mlp_bwd,
+    the one reader of go_e2, takes them through slot_map(pd); where that
+    kernel does not run, go_e2 is copied and the rows are written first."""
     z1, cg1, z2, cg2 = saved
     if isinstance(saved, list):
         saved.clear()
@@ -233,6 +239,11 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     ft2 = _fused_first_bwd(ops, packs_node, d)
     go_v2 = go_v2.contiguous() if go_v2 is not None else None
     go_e2 = go_e2.contiguous() if go_e2 is not None else None
+    if patch is not None and (go_v2 is None or ft2 is None or not getattr(
+            ops, "edge_mlp_bwd_patch", False)):
+        go_e2 = _own(go_e2)
+        _move_rows(ops, patch, pd.map_ude, go_e2, pd.map_de)
+        patch = None
     # factored weights that carry the graph: each reverse tail then returns
     # seg_dst(dz) as a third result, for _node_grad (sd1, sd2: [] without)
     if factored and need_gv and mlp_path.fused_seg(ops, d):
@@ -251,7 +262,11 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
         del z2, cg2
         # e2 grad: external + the node MLP's per-edge GEMM, fused.  The
         # result is a fresh buffer, never go_e2 itself
-        if ft2 is not None:
+        if patch is not None:
+            ge2 = ops.r_edge_mlp_bwd(
+                dz2, ft2, go_e2,
+                patch=(slot_map(pd, go_e2.shape[0]), patch.contiguous()))
+        elif ft2 is not None:
             ge2 = ops.r_edge_mlp_bwd(dz2, ft2, go_e2)
         else:
             ge2 = (torch.addmm(go_e2, dz2, we2) if go_e2 is not None
@@ -515,12 +530,18 @@ class _AtomBlockFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, v, e, bexp, Wbb, Wab, edge_mask, pd, ops, pe, pn, d):
+    def forward(ctx, v, e, bexp, Wbb, Wab, edge_mask, pd, ops, pe, pn, d,
+                holder=None):
         assert not (Wbb.requires_grad or Wab.requires_grad
                     or pe[0].requires_grad or pn[0].requires_grad)
         wbb, wab = _block_weights(ops, bexp, Wbb, Wab, edge_mask, d)
         ctx.set_materialize_grads(False)
         ctx.consts = (Wbb, Wab, edge_mask, pd, ops, pe, pn, d)
+        # the row exchange that follows this block may leave the exchanged
+        # rows of its e gradient to this block's backward (ExchangeHolder)
+        ctx.holder = holder
+        if holder is not None:
+            holder.bound = True
         ctx.kept = None
         if getattr(ctx, "keep", False):
             # _AtomBlockKeepFn: the keep-form forward the backward would
@@ -544,6 +565,7 @@ class _AtomBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go_v2, go_e2):
         Wbb, Wab, edge_mask, pd, ops, pe, pn, d = ctx.consts
+        patch = ctx.holder.receive(go_e2) if ctx.holder is not None else None
         with torch.no_grad():
             if getattr(ctx, "keep", False):
                 assert ctx.kept, "a keep block runs its backward once"
@@ -557,7 +579,8 @@ class _AtomBlockFn(torch.autograd.Function):
                                       saves_only=True)[2])
             gv, ge, dwbb, dwab = atom_bwd(
                 ops, pd, saved, pe, pn, d, wbb, wab, go_v2, go_e2,
-                need_gv=ctx.needs_input_grad[0])
+                need_gv=ctx.needs_input_grad[0], patch=patch)
+            del patch
             factored = _is_factored(wbb)
             del wbb, wab
             dbexp = None
@@ -572,7 +595,7 @@ class _AtomBlockFn(torch.autograd.Function):
                 if dwab is not None:
                     dbexp.addmm_(dwab, Wab)
         return (gv, ge, dbexp, None, None, None, None, None, None, None,
-                None)
+                None, None)
 
 
 class _AtomBlockKeepFn(_AtomBlockFn):
@@ -622,6 +645,74 @@ def _own(g):
     return g.clone(memory_format=torch.contiguous_format)
 
 
+def slot_map(pd, n_rows):
+    """int32 [n_rows]: slot[pd.map_de[i]] = pd.map_ude[i], -1 elsewhere; what
+    r_edge_mlp_bwd's patch reads the exchanged rows by.  A function of the
+    graph alone: built on first use and kept on pd for as long as pd holds
+    the same two maps."""
+    c = getattr(pd, "_slot", None)
+    if (c is None or c[0] is not pd.map_de or c[1] is not pd.map_ude
+            or c[2].shape[0] != n_rows):
+        slot = torch.full((n_rows,), -1, dtype=torch.int32,
+                          device=pd.map_de.device)
+        slot[pd.map_de] = pd.map_ude.to(torch.int32)
+        c = pd._slot = (pd.map_de, pd.map_ude, slot)
+    return c[2]
+
+
+class ExchangeHolder:
+    """What the reverse of one edge/bond boundary (block k -> edge_to_bond ->
+    bond block -> bond_to_edge -> block k+1) hands along without copying the
+    gradient of e.  One per boundary, shared by block k's _AtomBlockFn and the
+    two exchange Functions; runtime.atom_conv's caller wires it.
+
+    With a bound holder bond_to_edge's backward returns its incoming
+    gradient as it is (the rows pd.map_de are stale from there on: they
+    stand for zeros), edge_to_bond's backward returns it again and leaves
+    G_nc here (the stale rows now stand for G_nc[pd.map_ude]), and block k's
+    backward takes G_nc as the patch of atom_bwd.  Each hand-over records the
+    tensor it returned (the object, its data_ptr and _version) and the next
+    stage checks that this is what it received: the chain has one consumer
+    per stage, so anything else means that autograd summed or copied the
+    gradient on the way, and stale rows would leak.
+
+    bound is set by the block's forward: an exchange whose holder no block
+    took (the op-by-op block under a checkpoint) copies as without one."""
+
+    def __init__(self):
+        self.bound = False
+        self.patch = None
+        self._sent = None
+
+    def send(self, g, patch=None):
+        self._sent = (g, g.data_ptr(), g._version)
+        self.patch = patch
+
+    @property
+    def pending(self):
+        return self._sent is not None
+
+    def receive(self, g):
+        """The patch sent along with g (None: g is whole); raises if
+        something was sent and g is not it."""
+        if self._sent is None:
+            return None
+        (t, ptr, ver), patch = self._sent, self.patch
+        self._sent = self.patch = None
+        if (g is None or g.data_ptr() != ptr or g._version != ver
+                or g.shape != t.shape):
+            raise RuntimeError(
+                "lazy edge/bond exchange: the gradient of e that arrived is "
+                "not the tensor the exchange's reverse handed on (e has a "
+                "second consumer, or a hook copied its gradient), so its "
+                "exchanged rows are stale; set DM_NO_LAZY_EXCHANGE=1")
+        return patch
+
+
+def _lazy(holder):
+    return holder is not None and holder.bound
+
+
 class _EdgeToBondFn(torch.autograd.Function):
     """(e, n_prev) -> (e, n_c): n_c = n_prev.index_copy(map_ude, e[map_de]).
 
@@ -635,7 +726,7 @@ class _EdgeToBondFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, e, n_prev, pd, ops):
+    def forward(ctx, e, n_prev, pd, ops, holder=None):
         B, M = n_prev.shape[0], len(pd.map_ude)
         # map_ude is unique: with B == M it names every row
         n_c = torch.empty_like(n_prev, memory_format=torch.contiguous_format) \
@@ -644,21 +735,36 @@ class _EdgeToBondFn(torch.autograd.Function):
         ctx.mark_dirty(e)
         ctx.set_materialize_grads(False)
         ctx.pd, ctx.ops, ctx.e_shape = pd, ops, e.shape
+        ctx.holder = holder if _lazy(holder) else None
         return e, n_c
 
     @staticmethod
     def backward(ctx, G_e, G_nc):
-        pd, ops = ctx.pd, ctx.ops
+        pd, ops, holder = ctx.pd, ctx.ops, ctx.holder
+        # stale: bond_to_edge's reverse handed G_e on with the rows map_de
+        # still to be read as zeros
+        stale = holder is not None and holder.pending
+        if stale:
+            holder.receive(G_e)
         if G_nc is None:
-            return G_e, None, None, None
+            if stale and ctx.needs_input_grad[0]:
+                G_e = _own(G_e)
+                _zero_rows(ops, G_e, pd.map_de)
+            return G_e, None, None, None, None
         ge = gn = None
         if ctx.needs_input_grad[0]:
-            ge = _own(G_e) if G_e is not None else G_nc.new_zeros(ctx.e_shape)
-            _move_rows(ops, G_nc, pd.map_ude, ge, pd.map_de, add=True)
+            if stale:
+                # no copy: block k reads the rows map_de from G_nc
+                ge = G_e
+                holder.send(G_e, patch=G_nc)
+            else:
+                ge = _own(G_e) if G_e is not None \
+                    else G_nc.new_zeros(ctx.e_shape)
+                _move_rows(ops, G_nc, pd.map_ude, ge, pd.map_de, add=True)
         if ctx.needs_input_grad[1]:
             gn = _own(G_nc)
             _zero_rows(ops, gn, pd.map_ude)
-        return ge, gn, None, None
+        return ge, gn, None, None, None
 
 
 class _BondToEdgeFn(torch.autograd.Function):
@@ -666,10 +772,11 @@ class _BondToEdgeFn(torch.autograd.Function):
     (the out-of-place index_copy clones all of e to change 4M rows)."""
 
     @staticmethod
-    def forward(ctx, e, n2, pd, ops):
+    def forward(ctx, e, n2, pd, ops, holder=None):
         _move_rows(ops, n2, pd.map_ude, e, pd.map_de)
         ctx.mark_dirty(e)
         ctx.pd, ctx.ops, ctx.n_shape = pd, ops, n2.shape
+        ctx.holder = holder if _lazy(holder) else None
         return e
 
     @staticmethod
@@ -682,21 +789,28 @@ class _BondToEdgeFn(torch.autograd.Function):
                 else go.new_zeros(ctx.n_shape)
             _move_rows(ops, go, pd.map_de, gn2, pd.map_ude)
         if ctx.needs_input_grad[0]:
-            ge = _own(go)
-            _zero_rows(ops, ge, pd.map_de)
-        return ge, gn2, None, None
+            if ctx.holder is not None:
+                # no copy: the rows map_de are zeroed where they are read
+                ge = go
+                ctx.holder.send(go)
+            else:
+                ge = _own(go)
+                _zero_rows(ops, ge, pd.map_de)
+        return ge, gn2, None, None, None
 
 
-def edge_to_bond(e, n_prev, pd, ops):
+def edge_to_bond(e, n_prev, pd, ops, holder=None):
     """(e, n_c) with n_c = n_prev.index_copy(0, pd.map_ude, e[pd.map_de]);
     go on with the returned e (same storage) so that e keeps one consumer.
-    Only where no saved tensor aliases e: the checkpointed steps."""
-    return _EdgeToBondFn.apply(e, n_prev, pd, ops)
+    Only where no saved tensor aliases e: the checkpointed steps.  holder:
+    the ExchangeHolder of this boundary, given to the block that made e, to
+    bond_to_edge and here."""
+    return _EdgeToBondFn.apply(e, n_prev, pd, ops, holder)
 
 
-def bond_to_edge(e, n2, pd, ops):
+def bond_to_edge(e, n2, pd, ops, holder=None):
     """e.index_copy(0, pd.map_de, n2[pd.map_ude]) written in place over e."""
-    return _BondToEdgeFn.apply(e, n2, pd, ops)
+    return _BondToEdgeFn.apply(e, n2, pd, ops, holder)
 
 
 def atom_block_available(ops, pe, d, dtype) -> bool:

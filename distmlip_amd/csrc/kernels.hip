@@ -1526,11 +1526,27 @@ void k_gated_mlp_tail_bwd_seg(const float* __restrict__ go,
 // 7.39 against 8.73 for mm.  Indexed reverse tail in the same runs: 20.0 ms
 // in the trace against 22.4 + 3.1 (k_gather_rows_v4), 22.2 against 28.0
 // stand-alone.
+//
+// Patched gbase (k_edge_mlp_bwd<true, true>, dm_edge_mlp_bwd_patch_f32): row r
+// of gbase is read from patch[slot[r]] where slot[r] >= 0 and from gbase[r]
+// where it is -1.  It is the reverse of the edge/bond row exchange folded into
+// this read: the dense gradient with the exchanged rows replaced is never
+// built.  Lane c of a wave loads slot[base + c] (clamped like every load) with
+// the A operand, ahead of the MFMAs; the epilogue takes the slot of a row from
+// that register by v_readlane (the row of register r is a compile-time lane
+// number for each half of the wave) and selects the row pointer once per row.
+// Everything else is the <true> form: accumulator layout, k order, one
+// rounding of gbase + acc, clamped loads, predicated stores, 64-bit offsets.
+// out may still be gbase; patch must not overlap out (a patched row is read
+// through another tile's rows).  Extra bytes: slot, 4 per row.
+//   <true, true> (patched gbase): 114 VGPR, 0 AGPR, 66 SGPR, 32 KB LDS, 4
+//                    waves/SIMD, no scratch; <true> and <false> are unchanged
+//                    by the two extra (unused) kernel arguments.
 // ---------------------------------------------------------------------------
-template <bool HAS_BASE, bool FULL>
+template <bool HAS_BASE, bool FULL, bool PATCH = false>
 __device__ __forceinline__ void edge_mlp_bwd_epilogue(
         const f32x16 (&acc)[2], const float* gbase, float* out, int64_t base,
-        int64_t E, int c, int h) {
+        int64_t E, int c, int h, int sv = 0, const float* patch = nullptr) {
     constexpr int G = 8;
 #pragma unroll
     for (int rb = 0; rb < 16; rb += G) {
@@ -1543,6 +1559,14 @@ __device__ __forceinline__ void edge_mlp_bwd_epilogue(
                 const int64_t row = base + rl;
                 const int64_t lrow = (FULL || row < E) ? row : E - 1;
                 const float* gp = gbase + lrow * 64 + c;
+                if (PATCH) {
+                    // slot of row rl: lane rl holds it (clamped as lrow is)
+                    const int rl0 = (r & 3) + 8 * (r >> 2);
+                    const int s0 = __builtin_amdgcn_readlane(sv, rl0);
+                    const int s1 = __builtin_amdgcn_readlane(sv, rl0 + 4);
+                    const int sl = h ? s1 : s0;
+                    if (sl >= 0) gp = patch + (int64_t)sl * 64 + c;
+                }
                 gv[t][0] = gp[0];
                 gv[t][1] = gp[32];
             }
@@ -1562,13 +1586,16 @@ __device__ __forceinline__ void edge_mlp_bwd_epilogue(
     }
 }
 
-template <bool HAS_BASE>
+template <bool HAS_BASE, bool PATCH = false>
 __global__ __launch_bounds__(256, 3)
 void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
                     const float* __restrict__ WT,    // [64,128] row-major
                     const float* gbase,              // [E,64], HAS_BASE
                     float* out,                      // [E,64], may be gbase
-                    int64_t E) {
+                    int64_t E,
+                    const int32_t* __restrict__ slot = nullptr,  // [E], PATCH
+                    const float* patch = nullptr) {  // [M,64], PATCH
+    static_assert(HAS_BASE || !PATCH, "a patch replaces rows of gbase");
     __shared__ float2 wlds[128 * 32];
     // i = (col, k) with k fastest: coalesced reads of the row-major WT
     for (int i = threadIdx.x; i < 128 * 32; i += blockDim.x) {
@@ -1597,6 +1624,8 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
         float4 a[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) a[i] = ap[2 * i];
+        int sv = 0;
+        if (PATCH) sv = slot[lrow];
         __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
         f32x16 acc[2];
 #pragma unroll
@@ -1616,9 +1645,11 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
         }
         __builtin_amdgcn_s_setprio(0);
         if (base + 32 <= E)
-            edge_mlp_bwd_epilogue<HAS_BASE, true>(acc, gbase, out, base, E, c, h);
+            edge_mlp_bwd_epilogue<HAS_BASE, true, PATCH>(
+                acc, gbase, out, base, E, c, h, sv, patch);
         else
-            edge_mlp_bwd_epilogue<HAS_BASE, false>(acc, gbase, out, base, E, c, h);
+            edge_mlp_bwd_epilogue<HAS_BASE, false, PATCH>(
+                acc, gbase, out, base, E, c, h, sv, patch);
     }
 }
 
@@ -3272,6 +3303,31 @@ int dm_edge_mlp_bwd_f32(const float* dz, const float* WT, const float* gbase,
     else
         k_edge_mlp_bwd<false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
             dz, WT, nullptr, out, E);
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_edge_mlp_bwd_patch_f32(const float* dz, const float* WT,
+                              const float* gbase, const int32_t* slot,
+                              const float* patch, float* out, int64_t E,
+                              int64_t Din, int64_t Dout, uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (Din != 128 || Dout != 64) {
+        g_err = "edge_mlp_bwd fused kernel is compiled for Din=128, Dout=64";
+        return -1;
+    }
+    // patch may be NULL (an empty array) when no slot is >= 0
+    if (!gbase || !slot || !out) {
+        g_err = "edge_mlp_bwd_patch: gbase, slot and out must be given";
+        return -1;
+    }
+    if (patch == out) {
+        g_err = "edge_mlp_bwd_patch: patch must not be out";
+        return -1;
+    }
+    if (E <= 0) return 0;
+    k_edge_mlp_bwd<true, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+        dz, WT, gbase, out, E, slot, patch);
     DM_CHECK_LAUNCH();
     return 0;
 }

@@ -15,6 +15,8 @@ that call each other:
     whole-MLP kernel   needs the fused first layer and the fused tail forward
     factored weights   need both fused tails
     atom block         needs the fused first layer and no DM_FUSED_CONV
+    lazy exchange      needs the row exchange, the atom block and the fused
+                       first-layer reverse
 """
 from __future__ import annotations
 
@@ -168,6 +170,22 @@ def row_exchange() -> bool:
     """Checkpointed steps move edge/bond rows in place over e; the
     whole-graph Function does its own exchange."""
     return not is_set("DM_NO_ROW_EXCHANGE") and not whole_graph_ckpt()
+
+
+# DM_NO_LAZY_EXCHANGE=1: the reverses of the edge/bond row exchange each copy
+# the gradient of e and patch the exchanged rows, instead of leaving them to
+# the consuming block's first-layer reverse kernel.  Read at call time like
+# SWITCHES; it turns no other predicate off.
+NO_LAZY_EXCHANGE = "DM_NO_LAZY_EXCHANGE"
+
+
+def lazy_exchange(ops, d) -> bool:
+    """The reverses of the row exchange copy nothing: the block that consumes
+    the gradient of e reads the exchanged rows through r_edge_mlp_bwd's
+    patch (conv.ExchangeHolder)."""
+    return (os.environ.get(NO_LAZY_EXCHANGE, "0") != "1" and row_exchange()
+            and getattr(ops, "edge_mlp_bwd_patch", False)
+            and atom_block(ops, d) and fused_first_bwd(ops, d))
 
 
 def native_rows(ops) -> bool:

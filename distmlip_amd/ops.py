@@ -69,6 +69,10 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_edge_mlp_bwd_f32.restype = c_int32
         lib.dm_edge_mlp_bwd_f32.argtypes = [fp, fp, fp, fp, c_int64, c_int64,
                                             c_int64, c_uint64]
+        lib.dm_edge_mlp_bwd_patch_f32.restype = c_int32
+        lib.dm_edge_mlp_bwd_patch_f32.argtypes = [fp, fp, fp, ip, fp, fp,
+                                                  c_int64, c_int64, c_int64,
+                                                  c_uint64]
         lib.dm_gated_mlp_tail_fwd_f32.restype = c_int32
         lib.dm_gated_mlp_tail_fwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                   fp, fp, fp, c_int64,
@@ -477,12 +481,17 @@ class _GatherAdd3(torch.autograd.Function):
         return gzs, gzd, dz, None, None, None, None, None
 
 
-def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None):
+def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None, patch=None):
     """out = (gbase +) dz @ wt.t() in ONE kernel: the reverse of the fused
     first layer's per-edge GEMM, with the other gradient of the same rows
     added in its epilogue.  dz [E,128], wt [64,128] (the fusedT pack),
     gbase [E,64] or None.  out may be gbase (in place); only do that with a
-    buffer the caller owns."""
+    buffer the caller owns.
+
+    patch = (slot, rows): row r of gbase is read from rows[slot[r]] where
+    slot[r] >= 0 (slot int32 [E], -1 elsewhere; rows [M,64]; the entries are
+    not range-checked: that would cost a device round trip).  rows must not
+    share memory with out."""
     _chk_f32(dz, wt, gbase, out)
     E = dz.shape[0]
     assert dz.shape[1] == wt.shape[1]
@@ -490,6 +499,20 @@ def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None):
     if out is None:
         out = torch.empty(E, wt.shape[0], dtype=dz.dtype, device=dz.device)
     assert out.shape == (E, wt.shape[0])
+    if patch is not None:
+        slot, rows = patch
+        _chk_f32(rows)
+        assert gbase is not None, "a patch replaces rows of gbase"
+        assert slot.dtype == torch.int32 and slot.is_contiguous() \
+            and slot.device == dz.device and slot.shape == (E,)
+        assert rows.dim() == 2 and rows.shape[1] == wt.shape[0]
+        assert (rows.untyped_storage().data_ptr()
+                != out.untyped_storage().data_ptr()), \
+            "patch rows must not alias out"
+        _check(hip_lib().dm_edge_mlp_bwd_patch_f32(
+            _fp(dz), _fp(wt), _fp(gbase), _ip(slot), _fp(rows), _fp(out), E,
+            dz.shape[1], wt.shape[0], _stream()), "dm_edge_mlp_bwd_patch_f32")
+        return out
     _check(hip_lib().dm_edge_mlp_bwd_f32(
         _fp(dz), _fp(wt), _fp(gbase), _fp(out), E, dz.shape[1], wt.shape[0],
         _stream()), "dm_edge_mlp_bwd_f32")
@@ -1099,10 +1122,14 @@ class HipOps:
         the [64,128] fusedT pack only)."""
         return raw_edge_mlp3(erow, wt, bias, zs, zd, pd.src, pd.dst)
 
-    def r_edge_mlp_bwd(self, dz, wt, gbase=None, out=None):
+    # r_edge_mlp_bwd takes patch=(slot, rows)
+    edge_mlp_bwd_patch = True
+
+    def r_edge_mlp_bwd(self, dz, wt, gbase=None, out=None, patch=None):
         """(gbase +) dz @ wt.t() in one kernel (wt = the [64,128] fusedT
-        pack only); out may be gbase when the caller owns it."""
-        return raw_edge_mlp_bwd(dz, wt, gbase, out)
+        pack only); out may be gbase when the caller owns it.  patch =
+        (slot, rows): gbase row r is rows[slot[r]] where slot[r] >= 0."""
+        return raw_edge_mlp_bwd(dz, wt, gbase, out, patch)
 
     def r_move_rows(self, src, si, dst, di, add=False):
         """dst[di] (=|+=) src[si] by rows, in place over dst, one kernel;

@@ -79,7 +79,13 @@ the permutation CSRs the graph builder emits; `csr` is an optional
     r_edge_mlp_bwd(dz, wt, gbase, out)   -> (gbase +) dz @ wt.t(), its
                                             reverse with the gradient sum in
                                             the epilogue; out may be gbase.
-                                            OPTIONAL (wt [64,128])
+                                            OPTIONAL (wt [64,128]).  A backend
+                                            with the class attribute
+                                            edge_mlp_bwd_patch = True also
+                                            takes patch=(slot, rows): gbase
+                                            row r is rows[slot[r]] where the
+                                            int32 [E] slot is >= 0; rows must
+                                            not share memory with out
     r_move_rows(src, si, dst, di, add=False)
                                          -> dst, written IN PLACE:
                                             dst[di[i]] (=|+=) src[si[i]] by

@@ -33,7 +33,8 @@ import torch
 import torch.distributed as dist
 
 from distmlip_amd import mlp_path
-from distmlip_amd.conv import (_AtomBlockFn, _AtomBlockKeepFn, _AtomConvFn,
+from distmlip_amd.conv import (ExchangeHolder, _AtomBlockFn,
+                               _AtomBlockKeepFn, _AtomConvFn,
                                _BondConvFn, atom_block_available,
                                bond_to_edge, conv_fn_available, edge_to_bond)
 from distmlip_amd.chgnet import (
@@ -522,7 +523,7 @@ class SpmdEngine:
             v = ops.scatter_edges(msg, pd, base=v)
             return v, e
 
-        def atom_conv(layer_i, v, e):
+        def atom_conv(layer_i, v, e, holder=None):
             if ckpt:
                 # checkpointed steps: the block recomputes itself (lean
                 # outer forward, hand-sequenced reverse) where it can
@@ -541,7 +542,7 @@ class SpmdEngine:
                         else _AtomBlockFn
                     return fn.apply(
                         v, e, bond_expansion, wbb_w, wab_w, edge_mask, pd,
-                        ops, pe, _packed_weights(blk.node_mlp), d)
+                        ops, pe, _packed_weights(blk.node_mlp), d, holder)
             return _ck(atom_conv_body,
                        torch.tensor(layer_i % cfg.n_blocks), v, e,
                        bond_expansion)
@@ -586,10 +587,16 @@ class SpmdEngine:
                                 site_props, calc_stresses, P)
 
         for layer_i in range(cfg.n_blocks - 1):           # chgnet.py:296-368
-            v, e = atom_conv(layer_i, v, e)
+            # one holder per boundary: the two exchange reverses then copy
+            # nothing, and this block's backward reads the exchanged rows of
+            # its e gradient from the bond side (conv.ExchangeHolder); a
+            # block that does not take it leaves it unbound and unused
+            holder = ExchangeHolder() if (
+                row_x and mlp_path.lazy_exchange(ops, d)) else None
+            v, e = atom_conv(layer_i, v, e, holder)
             if use_bg:
                 if row_x:
-                    e, n = edge_to_bond(e, n, pd, ops)
+                    e, n = edge_to_bond(e, n, pd, ops, holder)
                 else:
                     n = n.index_copy(0, pd.map_ude, e[pd.map_de])  # edge_to_bond
                 n = _halo(n, line_plan)
@@ -623,7 +630,7 @@ class SpmdEngine:
 
                 n = _ck(bond_body, n, a, v, exp3)
                 if row_x:
-                    e = bond_to_edge(e, n, pd, ops)
+                    e = bond_to_edge(e, n, pd, ops, holder)
                 else:
                     e = e.index_copy(0, pd.map_de, n[pd.map_ude])  # bond_to_edge
 

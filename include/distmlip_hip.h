@@ -163,6 +163,19 @@ int dm_edge_mlp_bwd_f32(const float* dz, const float* WT, const float* gbase,
                         float* out, int64_t E, int64_t Din, int64_t Dout,
                         uint64_t stream);
 
+/* dm_edge_mlp_bwd_f32 with rows of gbase replaced on the fly: row e of gbase
+ * is read from patch[slot[e]] where slot[e] >= 0 and from gbase[e] where
+ * slot[e] == -1, i.e. the plain entry on a copy of gbase with those rows
+ * overwritten, bit for bit, without that [E,Dout] copy being made.  slot is
+ * int32 [E], every entry -1 or a row of patch [M,Dout] (not checked).  out may
+ * be gbase itself; patch must not overlap out.  patch may be NULL when no
+ * slot is >= 0.  Same refusals as dm_edge_mlp_bwd_f32; gbase, slot and out
+ * must not be NULL. */
+int dm_edge_mlp_bwd_patch_f32(const float* dz, const float* WT,
+                              const float* gbase, const int32_t* slot,
+                              const float* patch, float* out, int64_t E,
+                              int64_t Din, int64_t Dout, uint64_t stream);
+
 /* Fused forward tail of one gated MLP: the second layer over h [E,2d] and
  * the combine, in one kernel:
  *   c = h[:, :d] @ w2c + b2c        g = h[:, d:] @ w2g + b2g
