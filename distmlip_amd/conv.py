@@ -27,7 +27,10 @@ tail; 1205-1210 -> 1096-1102 ms/step at si1m (profiles/first_bwd_*).
 Their final block keeps its saves (_AtomBlockKeepFn), and the 4M rows that
 move between e and n around every bond block go through edge_to_bond /
 bond_to_edge, in place over e (1011-1014 -> 909-914 ms/step,
-profiles/row_exchange_*).
+profiles/row_exchange_*).  Their bond and angle blocks are _BondBlockFn /
+_AngleBlockFn, the same kind of node over bond_fwd / bond_bwd and angle_fwd /
+angle_bwd with the one-kernel three-gather MLP and the line weights read
+from w3 through l_src (793-799 -> 755-759 ms/step, profiles/line_block_*).
 """
 from __future__ import annotations
 
@@ -75,12 +78,15 @@ def _records(*ts):
         t is not None and t.requires_grad for t in ts)
 
 
-def _mlp_tail_act(ops, h, w2, b2, w, base, d):
+def _mlp_tail_act(ops, h, w2, b2, w, base, d, w_idx=None):
     """out of _mlp_tail_fwd alone, for the save-nothing forwards: no cg is
-    written where mlp_path allows mlp_tail_act."""
+    written where mlp_path allows mlp_tail_act.  w_idx (that form only): w is
+    a table read by index."""
     if (not _records(h, w, base)
             and mlp_path.fused_tail_fwd(ops, d, "mlp_tail_act")):
-        return ops.mlp_tail_act(h, w2, b2, w, base)
+        kw = {"w_idx": w_idx} if w_idx is not None else {}
+        return ops.mlp_tail_act(h, w2, b2, w, base, **kw)
+    assert w_idx is None
     return ops.gated_combine_packed(_second_fwd(h, w2, b2, d), w, base)
 
 
@@ -348,36 +354,95 @@ def conv_fn_available(ops, mlp_pack, prim="r_gather_add3") -> bool:
             and torch.is_grad_enabled())
 
 
-def bond_fwd(ops, pd, n, a, v, w3, packs, d, mask_l=None):
-    """One bond (line-graph) node conv forward (chgnet.py:326-348).
-    Returns (n2, saved) with saved = (z, cg, wl)."""
+def _line_fwd(ops, pd, n, a, v, packs, d, w, base, w_idx=None,
+              want_out=True):
+    """(z, cg, out) of one line-graph gated MLP in keep form.  With a 5-pack
+    and the fused first layer (_line_fused): one kernel where mlp_path allows
+    r_gated_mlp4, else r_edge_mlp4 + r_mlp_tail_fwd, the same bits; w may
+    then be a table read by w_idx, and want_out=False lets the one-kernel
+    form skip out (w and base are not read).  Else the rocBLAS first layer +
+    r_gather_add4 followed by the tail."""
     w1, wn2, wa, wv, bcg, w2, b2 = _unpack_line(packs, d)
+    if _line_fused(ops, packs, d):
+        first = (a.contiguous(), packs[4], bcg, n @ w1.t(), n @ wn2.t(),
+                 v @ wv.t(), pd)
+        if mlp_path.whole_mlp4_keep(ops, d):
+            return ops.r_gated_mlp4(*first, w2, b2, w, base, w_idx, want_out)
+        z, h = ops.r_edge_mlp4(*first)
+        kw = {"w_idx": w_idx} if w_idx is not None else {}
+        cg, out = ops.r_mlp_tail_fwd(h, w2, b2, w, base, **kw)
+        return z, cg, out
+    assert w_idx is None and want_out
+    z, h = ops.r_gather_add4(n @ w1.t(), n @ wn2.t(),
+                             torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
+    cg, out = _mlp_tail_fwd(ops, h, w2, b2, w, base, d)
+    return z, cg, out
+
+
+def _line_fused(ops, packs, d):
+    return (_fusedT(packs) is not None
+            and mlp_path.fused_first(ops, d, "r_edge_mlp4")
+            and mlp_path.fused_tail_fwd(ops, d))
+
+
+def bond_fwd(ops, pd, n, a, v, w3, packs, d, mask_l=None, saves_only=False):
+    """One bond (line-graph) node conv forward (chgnet.py:326-348).
+    Returns (n2, saved) with saved = (z, cg, wl).  With a 5-pack, no mask and
+    a backend with the fused first layer and w_idx, the MLP reads w3 through
+    pd.l_src: wl is never built and saved[2] is None (bond_bwd then takes
+    w3).  saves_only=True (a recomputation, that form only) returns
+    (None, saved): the segment sum of msg is skipped."""
+    if (mask_l is None and _line_fused(ops, packs, d)
+            and getattr(ops, "w_idx", False)):
+        z, cg, msg = _line_fwd(ops, pd, n, a, v, packs, d, w3.contiguous(),
+                               None, pd.l_src, want_out=not saves_only)
+        n2 = ops.r_seg_ldst(msg, pd, base=n) if not saves_only else None
+        return n2, (z, cg, None)
+    assert not saves_only
     wl = ops.r_gather_lsrc(w3, pd)
     if mask_l is not None:
         wl = wl * mask_l
-    z, h = ops.r_gather_add4(n @ w1.t(), n @ wn2.t(),
-                             torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
-    cg, msg = _mlp_tail_fwd(ops, h, w2, b2, wl, None, d)
+    z, cg, msg = _line_fwd(ops, pd, n, a, v, packs, d, wl, None)
     n2 = ops.r_seg_ldst(msg, pd, base=n)
     return n2, (z, cg, wl)
 
 
 def bond_bwd(ops, pd, saved, packs, d, go_n2, mask_l=None,
-             acc_w3=None, acc_a=None, acc_v=None):
+             acc_w3=None, acc_a=None, acc_v=None, w3=None):
     """Hand-sequenced reverse of bond_fwd.  Returns (gn, da, gv, gw3);
-    da/gv/gw3 are accumulated into acc_* buffers (add_) when given."""
+    da/gv/gw3 are accumulated into acc_* buffers (add_) when given.
+
+    saved[2] None (bond_fwd's one-kernel form; w3 is then given): the tail
+    reads w3 through pd.l_src and go_n2 through pd.l_dst instead of two
+    gathered [L,d] copies, and returns r_seg_ldst(dz) from its epilogue where
+    mlp_path.line_seg allows.  With a 5-pack and r_edge_mlp_bwd, da is that
+    kernel.  saved may be a list: it is emptied."""
     z, cg, wl = saved
+    if isinstance(saved, list):
+        saved.clear()
     w1, wn2, wa, wv, _, w2, _ = _unpack_line(packs, d)
+    ft = _fused_first_bwd(ops, packs, d)
     go_n2 = go_n2.contiguous()
-    dmsg = ops.r_gather_ldst(go_n2, pd)
-    dz, dwl = _mlp_tail_bwd(ops, dmsg, cg, wl, z, w2, d)
+    sd = []
+    if wl is None:
+        from .ops import LineSeg
+        seg = LineSeg(pd) if mlp_path.line_seg(ops, d) else None
+        dz, dwl, *sd = ops.r_mlp_tail_bwd(go_n2, cg, w3.contiguous(), z, w2,
+                                          pd.l_dst, w_idx=pd.l_src, seg=seg)
+    else:
+        dmsg = ops.r_gather_ldst(go_n2, pd)
+        dz, dwl = _mlp_tail_bwd(ops, dmsg, cg, wl, z, w2, d)
+        del dmsg
+    del z, cg, wl
     if acc_a is not None:
         acc_a.addmm_(dz, wa)
         da = None
+    elif ft is not None:
+        da = ops.r_edge_mlp_bwd(dz, ft)
     else:
         da = dz @ wa
     gn = torch.addmm(go_n2, ops.r_seg_lsrc(dz, pd), w1)
-    gn.addmm_(ops.r_seg_ldst(dz, pd), wn2)
+    gn.addmm_(sd[0] if sd else ops.r_seg_ldst(dz, pd), wn2)
     if acc_v is not None:
         acc_v.addmm_(ops.r_seg_center(dz, pd), wv)
         gv = None
@@ -393,24 +458,32 @@ def bond_bwd(ops, pd, saved, packs, d, go_n2, mask_l=None,
     return gn, da, gv, gw3
 
 
-def angle_fwd(ops, pd, n, a, v, packs, d):
+def angle_fwd(ops, pd, n, a, v, packs, d, saves_only=False):
     """Angle (line-edge) update forward: a2 = a + GatedMLP(cat(n_lsrc,
-    n_ldst, a, v_center)) (chgnet.py:350-368).  Returns (a2, saved)."""
-    w1, wn2, wa, wv, bcg, w2, b2 = _unpack_line(packs, d)
-    z, h = ops.r_gather_add4(n @ w1.t(), n @ wn2.t(),
-                             torch.addmm(bcg, a, wa.t()), v @ wv.t(), pd)
-    cg, a2 = _mlp_tail_fwd(ops, h, w2, b2, None, a, d)
+    n_ldst, a, v_center)) (chgnet.py:350-368).  Returns (a2, saved).
+    saves_only=True (a recomputation; one-kernel form of _line_fwd only):
+    (None, saved), a2 is not computed."""
+    assert not saves_only or _line_fused(ops, packs, d)
+    z, cg, a2 = _line_fwd(ops, pd, n, a, v, packs, d, None, a,
+                          want_out=not saves_only)
     return a2, (z, cg)
 
 
 def angle_bwd(ops, pd, saved, packs, d, go_a2, acc_n=None, acc_v=None):
     """Reverse of angle_fwd.  Returns (gn, da, gv); gn/gv accumulate into
-    acc_* when given (da is the full pass-through + wa chain)."""
+    acc_* when given (da is the full pass-through + wa chain: one
+    r_edge_mlp_bwd with a 5-pack).  saved may be a list: it is emptied."""
     z, cg = saved
+    if isinstance(saved, list):
+        saved.clear()
     w1, wn2, wa, wv, _, w2, _ = _unpack_line(packs, d)
+    ft = _fused_first_bwd(ops, packs, d)
     go_a2 = go_a2.contiguous()
     dz, _ = _mlp_tail_bwd(ops, go_a2, cg, None, z, w2, d)
-    da = torch.addmm(go_a2, dz, wa)
+    del z, cg
+    # a fresh buffer, never go_a2 itself
+    da = ops.r_edge_mlp_bwd(dz, ft, go_a2) if ft is not None \
+        else torch.addmm(go_a2, dz, wa)
     if acc_n is not None:
         gn = None
         acc_n.addmm_(ops.r_seg_lsrc(dz, pd), w1)
@@ -822,25 +895,106 @@ def atom_block_available(ops, pe, d, dtype) -> bool:
             and torch.is_grad_enabled())
 
 
-def _lean_line(ops, pd, n, a, v, packs, d, w, base):
+def _lean_line(ops, pd, n, a, v, packs, d, w, base, w_idx=None):
     """Save-nothing line-graph gated MLP: one kernel where mlp_path allows
-    gated_mlp4_act and nothing records, else first layer + tail."""
+    gated_mlp4_act and nothing records, else first layer + tail.  w_idx (with
+    a fused tail): w is a table read by index."""
     if mlp_path.whole_mlp_act(ops, d) and not _records(n, a, v, w):
         w1, wn2, _, wv, bcg, w2, b2 = _unpack_line(packs, d)
+        kw = {"w_idx": w_idx} if w_idx is not None else {}
         return ops.gated_mlp4_act(a, packs[4], bcg, n @ w1.t(), n @ wn2.t(),
-                                  v @ wv.t(), pd, w2, b2, w, base)
+                                  v @ wv.t(), pd, w2, b2, w, base, **kw)
     return _mlp_tail_act(ops, first4(ops, pd, n, a, v, packs, d), packs[2],
-                         packs[3], w, base, d)
+                         packs[3], w, base, d, w_idx)
 
 
-def _lean_bond(ops, pd, n, a, v, w3, pb, d):
-    wl = ops.gather(w3, pd.l_src, csr=pd.line_src_csr)
-    return ops.scatter_lines(_lean_line(ops, pd, n, a, v, pb, d, wl, None),
-                             pd, base=n)
+def _lean_bond(ops, pd, n, a, v, w3, pb, d, indexed=False):
+    """indexed: the MLP reads w3 through pd.l_src instead of a gathered
+    [L,d] copy (mlp_path.line_block)."""
+    if indexed:
+        msg = _lean_line(ops, pd, n, a, v, pb, d, w3, None, pd.l_src)
+    else:
+        wl = ops.gather(w3, pd.l_src, csr=pd.line_src_csr)
+        msg = _lean_line(ops, pd, n, a, v, pb, d, wl, None)
+    return ops.scatter_lines(msg, pd, base=n)
 
 
 def _lean_angle(ops, pd, n, a, v, pa, d):
     return _lean_line(ops, pd, n, a, v, pa, d, None, a)
+
+
+def line_block_available(ops, pb, d, dtype) -> bool:
+    """Self-recomputing line-graph block policy for checkpointed steps: fp32,
+    frozen weights, recording mode, and mlp_path.line_block."""
+    return (mlp_path.line_block(ops, d) and dtype == torch.float32
+            and not pb[0].requires_grad
+            and torch.is_grad_enabled())
+
+
+class _BondBlockFn(torch.autograd.Function):
+    """(n, a, v, exp3) -> n' for one bond block of a checkpointed step without
+    a bond mask: a self-recomputing node in place of torch.utils.checkpoint
+    around runtime's op-by-op bond_body, as _AtomBlockFn is for the atom
+    block.
+
+    The forward is the save-nothing _lean_bond with the line weights read
+    from w3 [B,d] through pd.l_src (no [L,d] copy) and keeps n, a, v and
+    exp3; the backward rebuilds w3, recomputes z and cg with one kernel
+    (bond_fwd, saves_only) and runs bond_bwd.  W3 is the [d, n_rbf] weight of
+    the bias-free threebody_bond_weights linear and must be frozen, like the
+    5-pack pb."""
+
+    @staticmethod
+    def forward(ctx, n, a, v, exp3, W3, pd, ops, pb, d):
+        assert not (W3.requires_grad or pb[0].requires_grad)
+        ctx.set_materialize_grads(False)
+        ctx.consts = (W3, pd, ops, pb, d)
+        w3 = torch.nn.functional.linear(exp3.detach(), W3)
+        n2 = _lean_bond(ops, pd, n.detach(), a.detach(), v.detach(), w3, pb,
+                        d, indexed=True)
+        ctx.save_for_backward(n, a, v, exp3)
+        return n2
+
+    @staticmethod
+    def backward(ctx, go_n2):
+        W3, pd, ops, pb, d = ctx.consts
+        n, a, v, exp3 = ctx.saved_tensors
+        if go_n2 is None:
+            return (None,) * 9
+        with torch.no_grad():
+            w3 = torch.nn.functional.linear(exp3, W3)
+            saved = list(bond_fwd(ops, pd, n, a, v, w3, pb, d,
+                                  saves_only=True)[1])
+            gn, da, gv, gw3 = bond_bwd(ops, pd, saved, pb, d, go_n2, w3=w3)
+            dexp3 = gw3 @ W3 if ctx.needs_input_grad[3] else None
+        return gn, da, gv, dexp3, None, None, None, None, None
+
+
+class _AngleBlockFn(torch.autograd.Function):
+    """(n, a, v) -> a' for one angle update of a checkpointed step, the same
+    way: the save-nothing _lean_angle forward, and a backward that recomputes
+    z and cg with one kernel (angle_fwd, saves_only) and runs angle_bwd."""
+
+    @staticmethod
+    def forward(ctx, n, a, v, pd, ops, pa, d):
+        assert not pa[0].requires_grad
+        ctx.set_materialize_grads(False)
+        ctx.consts = (pd, ops, pa, d)
+        a2 = _lean_angle(ops, pd, n.detach(), a.detach(), v.detach(), pa, d)
+        ctx.save_for_backward(n, a, v)
+        return a2
+
+    @staticmethod
+    def backward(ctx, go_a2):
+        pd, ops, pa, d = ctx.consts
+        n, a, v = ctx.saved_tensors
+        if go_a2 is None:
+            return (None,) * 7
+        with torch.no_grad():
+            saved = list(angle_fwd(ops, pd, n, a, v, pa, d,
+                                   saves_only=True)[1])
+            gn, da, gv = angle_bwd(ops, pd, saved, pa, d, go_a2)
+        return gn, da, gv, None, None, None, None
 
 
 def _edge_to_bond(pd, n, e):

@@ -972,6 +972,12 @@ __global__ void k_gated_combine_bwd(const float* __restrict__ go,
 //   since then <2> takes 214 VGPR, the dense forms 153 / 148 as before it)
 //   k_gated_mlp_tail_bwd_seg (seg_tile_sums in the epilogue, no packed fp32
 //   forms): <1> 158 VGPR, <2> 160, 0 AGPR, no scratch, 3 waves/SIMD
+// Indexed w (WIDX, dm_gated_mlp_tail_bwd_widx_f32): the dense w is a [T,64]
+// table and the lane, which owns its row, loads its own widx[r]; dw stays one
+// row per r.  <1, IDX, true>: 153 VGPR, 0 AGPR, 80-82 SGPR, 32 KB LDS, 3
+// waves/SIMD, no scratch; k_gated_mlp_tail_bwd_seg<1, IDX, true>: 158 VGPR,
+// 94-96 SGPR, the same otherwise: the figures of the forms without WIDX,
+// which are unchanged.
 // Indexed form (IDX, dm_gated_mlp_tail_bwd_idx_f32): go is a [N,64] table
 // and row r reads table row idx[r], one int32 index per lane per tile, loaded
 // inside the live predicate.  This is the reverse of a segment sum feeding
@@ -1093,7 +1099,8 @@ __device__ __forceinline__ void radial_stage_W(float* __restrict__ wl9,
 
 // A phase of one tile for one lane: dc|dg of the 32 floats it owns of its
 // row (offset off = row * 64 + 4h), dw stored from there.  go is read at
-// goff: off itself, or idx[row] * 64 + 4h in the indexed form.
+// goff: off itself, or idx[row] * 64 + 4h in the indexed form; the dense w
+// at woff: off itself, or widx[row] * 64 + 4h where w is a table (WIDX).
 // HAS_W == 2: w of the lane's 32 columns comes from its bexp row bx (9
 // registers) and mask m, and the W rows of those columns, the same for all
 // lanes of a half-wave, from LDS (wl9 points at row 4h: broadcast reads);
@@ -1102,7 +1109,7 @@ template <int HAS_W>
 __device__ __forceinline__ void mlp_tail_a_phase(
         const float* __restrict__ go, const float* __restrict__ cp,
         const float* __restrict__ gp, const float* __restrict__ wp,
-        float* __restrict__ dw, int64_t off, int64_t goff,
+        float* __restrict__ dw, int64_t off, int64_t goff, int64_t woff,
         float (&dcv)[32], float (&dgv)[32],
         const float4* __restrict__ wl9, const float (&bx)[N_RBF], float m,
         float (&dbp)[N_RBF]) {
@@ -1117,7 +1124,8 @@ __device__ __forceinline__ void mlp_tail_a_phase(
             vgo[j] = *(const float4*)(go + goff + 8 * (i0 + j));
             vc[j] = *(const float4*)(cp + o);
             vg[j] = *(const float4*)(gp + o);
-            if (HAS_W == 1) vw[j] = *(const float4*)(wp + o);
+            if (HAS_W == 1)
+                vw[j] = *(const float4*)(wp + woff + 8 * (i0 + j));
         }
         __builtin_amdgcn_sched_barrier(0);   // the batch in flight first
         // one range test per batch and the slice loop in two copies: a test
@@ -1307,7 +1315,7 @@ __global__ void k_seg_fixup(const double* __restrict__ part,
 }
 
 // The reverse tail's body; SEG adds seg_tile_sums over dz (seg, sums, part).
-template <int HAS_W, bool IDX, bool SEG>
+template <int HAS_W, bool IDX, bool SEG, bool WIDX = false>
 __device__ __forceinline__
 void gated_mlp_tail_bwd_body(const float* __restrict__ go,   // [E,64]; IDX: [N,64]
                           const int32_t* __restrict__ idx, // [E], IDX only
@@ -1330,7 +1338,11 @@ void gated_mlp_tail_bwd_body(const float* __restrict__ go,   // [E,64]; IDX: [N,
                           // SEG only
                           const int32_t* __restrict__ seg,   // [E]
                           float* __restrict__ sums,          // [N,128]
-                          double* __restrict__ part) {  // [tiles,2,128]
+                          double* __restrict__ part,    // [tiles,2,128]
+                          // WIDX only: wp is a [T,64] table, row r takes
+                          // wp[widx[r]]; dw stays one row per r
+                          const int32_t* __restrict__ widx = nullptr) {
+    static_assert(!WIDX || HAS_W == 1, "an indexed w is a dense table");
     __shared__ float4 wlds[64 * 32];
     __shared__ float4 wl9[HAS_W == 2 ? 64 * RBF_PAD / 4 : 1];
     if (HAS_W == 2) radial_stage_W((float*)wl9, fwW);
@@ -1373,12 +1385,14 @@ void gated_mlp_tail_bwd_body(const float* __restrict__ go,   // [E,64]; IDX: [N,
         if (live) {
             // IDX: row r's go is row idx[r] of a table, one index per lane
             const int64_t goff = IDX ? (int64_t)idx[r] * 64 + 4 * h : off;
+            const int64_t woff = WIDX ? (int64_t)widx[r] * 64 + 4 * h : off;
             if (HAS_W == 2) {
 #pragma unroll
                 for (int k = 0; k < N_RBF; ++k) bx[k] = wp[r * N_RBF + k];
                 if (fwmask) msk = fwmask[r];
             }
-            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, goff, dcv, dgv,
+            mlp_tail_a_phase<HAS_W>(go, cp, gp, wp, dw, off, goff, woff, dcv,
+                                    dgv,
                                     wl9 + (4 * h) * (RBF_PAD / 4), bx, msk,
                                     dbp);
         }
@@ -1433,7 +1447,7 @@ void gated_mlp_tail_bwd_body(const float* __restrict__ go,   // [E,64]; IDX: [N,
     }
 }
 
-template <int HAS_W, bool IDX>
+template <int HAS_W, bool IDX, bool WIDX = false>
 __global__ __launch_bounds__(256, HAS_W == 2 ? DM_FW_BWD_WAVES : 3)
 void k_gated_mlp_tail_bwd(const float* __restrict__ go,
                           const int32_t* __restrict__ idx,
@@ -1446,10 +1460,11 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,
                           float* __restrict__ dz, float* __restrict__ dw,
                           int64_t E, const float* __restrict__ fwW,
                           const float* __restrict__ fwmask,
-                          const float* dbexp_in, float* dbexp) {
-    gated_mlp_tail_bwd_body<HAS_W, IDX, false>(
+                          const float* dbexp_in, float* dbexp,
+                          const int32_t* __restrict__ widx = nullptr) {
+    gated_mlp_tail_bwd_body<HAS_W, IDX, false, WIDX>(
         go, idx, cp, gp, wp, z, w2c, w2g, dz, dw, E, fwW, fwmask, dbexp_in,
-        dbexp, nullptr, nullptr, nullptr);
+        dbexp, nullptr, nullptr, nullptr, widx);
 }
 
 // The SEG form is a kernel of its own so that it alone is compiled without
@@ -1461,7 +1476,7 @@ void k_gated_mlp_tail_bwd(const float* __restrict__ go,
 #define DM_NO_PK_F32
 #endif
 
-template <int HAS_W, bool IDX>
+template <int HAS_W, bool IDX, bool WIDX = false>
 __global__ __launch_bounds__(256, HAS_W == 2 ? DM_FW_BWD_WAVES : 3)
 DM_NO_PK_F32
 void k_gated_mlp_tail_bwd_seg(const float* __restrict__ go,
@@ -1478,10 +1493,11 @@ void k_gated_mlp_tail_bwd_seg(const float* __restrict__ go,
                               const float* dbexp_in, float* dbexp,
                               const int32_t* __restrict__ seg,
                               float* __restrict__ sums,
-                              double* __restrict__ part) {
-    gated_mlp_tail_bwd_body<HAS_W, IDX, true>(
+                              double* __restrict__ part,
+                              const int32_t* __restrict__ widx = nullptr) {
+    gated_mlp_tail_bwd_body<HAS_W, IDX, true, WIDX>(
         go, idx, cp, gp, wp, z, w2c, w2g, dz, dw, E, fwW, fwmask, dbexp_in,
-        dbexp, seg, sums, part);
+        dbexp, seg, sums, part, widx);
 }
 
 // ---------------------------------------------------------------------------
@@ -1691,6 +1707,11 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
 // The four factored-w variants <KEEP, 2, HAS_BASE>
 // (dm_gated_mlp_tail_fwd_fw_f32): 162 VGPR, 0 AGPR, 50-86 SGPR, 41 KB LDS
 // (W image 3 KB, bexp regions 6 KB), 3 waves/SIMD, no scratch.
+// The four indexed-w variants <KEEP, 1, HAS_BASE, true>
+// (dm_gated_mlp_tail_fwd_widx_f32; w is a table, row r takes w[widx[r]], see
+// mlp_tail_fwd_loads): 154 VGPR, 0 AGPR, 42-74 SGPR, 32 KB LDS, 3 waves/SIMD,
+// no scratch; the twelve variants above keep their VGPRs, LDS, occupancy and
+// no scratch with the extra argument (<true, 1, true>: 70 -> 44 SGPR).
 // Measured at si1m (rocprofv3 kernel trace, 3 steps; every launch there is a
 // KEEP one): at E = 46M rows with w and base, 24 launches, 13.8 ms average
 // (13.65-14.43); with w alone 12.85 ms (12.68-12.98); at L = 12M rows 3.8
@@ -1767,11 +1788,18 @@ __device__ __forceinline__ void radial_lane_W(
     radial_row(wl9 + (32 + c) * (RBF_PAD / 4), wc[1], pad);
 }
 
-template <int HAS_W, bool HAS_BASE, bool FULL, int G>
+// WIDX (HAS_W == 1): w is a [T,64] table and row r takes w[widx[r]].  wsv is
+// widx[base + c] (clamped like every load), loaded by lane c of both
+// half-waves; the index of a row comes out of that register by v_readlane
+// (the row of register r is a compile-time lane number for each half of the
+// wave, as in edge_mlp_bwd_epilogue's patch) and picks the row pointer once
+// per row.
+template <int HAS_W, bool HAS_BASE, bool FULL, int G, bool WIDX = false>
 __device__ __forceinline__ void mlp_tail_fwd_loads(
         float (&wv)[G][2], float (&bv)[G][2], int rb,
         const float* __restrict__ w, const float* __restrict__ bs,
-        int64_t base, int64_t E, int c, int h) {
+        int64_t base, int64_t E, int c, int h, int wsv = 0) {
+    static_assert(!WIDX || HAS_W == 1, "an indexed w is a dense table");
 #pragma unroll
     for (int t = 0; t < G; ++t) {
         const int r = rb + t;
@@ -1779,8 +1807,15 @@ __device__ __forceinline__ void mlp_tail_fwd_loads(
         const int64_t row = base + rl;
         const int64_t lrow = (FULL || row < E) ? row : E - 1;
         if (HAS_W == 1) {
-            wv[t][0] = w[lrow * 64 + c];
-            wv[t][1] = w[lrow * 64 + 32 + c];
+            const float* wr = w + lrow * 64 + c;
+            if (WIDX) {
+                const int rl0 = (r & 3) + 8 * (r >> 2);
+                const int s0 = __builtin_amdgcn_readlane(wsv, rl0);
+                const int s1 = __builtin_amdgcn_readlane(wsv, rl0 + 4);
+                wr = w + (int64_t)(h ? s1 : s0) * 64 + c;
+            }
+            wv[t][0] = wr[0];
+            wv[t][1] = wr[32];
         }
         if (HAS_BASE) {
             bv[t][0] = bs[lrow * 64 + c];
@@ -1845,28 +1880,29 @@ __device__ __forceinline__ void mlp_tail_fwd_rows(
     }
 }
 
-template <bool KEEP, int HAS_W, bool HAS_BASE, bool FULL>
+template <bool KEEP, int HAS_W, bool HAS_BASE, bool FULL, bool WIDX = false>
 __device__ __forceinline__ void mlp_tail_fwd_epilogue(
         const f32x16 (&acc)[4], const float4 bcol,
         const float* __restrict__ w, const float* __restrict__ bs,
         float* __restrict__ cout, float* __restrict__ gout,
         float* __restrict__ out, int64_t base, int64_t E, int c, int h,
-        const float4* __restrict__ wl9, const float4* __restrict__ st4) {
+        const float4* __restrict__ wl9, const float4* __restrict__ st4,
+        int wsv = 0) {
     constexpr int G = 8;
     float wc[2][N_RBF];
     if (HAS_W == 2) radial_lane_W(wc, wl9, c);
 #pragma unroll
     for (int rb = 0; rb < 16; rb += G) {
         float wv[G][2], bv[G][2];
-        mlp_tail_fwd_loads<HAS_W, HAS_BASE, FULL, G>(wv, bv, rb, w, bs, base,
-                                                     E, c, h);
+        mlp_tail_fwd_loads<HAS_W, HAS_BASE, FULL, G, WIDX>(
+            wv, bv, rb, w, bs, base, E, c, h, wsv);
         __builtin_amdgcn_sched_barrier(0);
         mlp_tail_fwd_rows<KEEP, HAS_W, HAS_BASE, FULL, true, G>(
             acc, bcol, wv, bv, rb, cout, gout, out, base, E, c, h, st4, wc);
     }
 }
 
-template <bool KEEP, int HAS_W, bool HAS_BASE>
+template <bool KEEP, int HAS_W, bool HAS_BASE, bool WIDX = false>
 __global__ __launch_bounds__(256, 3)
 void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
                           const float* __restrict__ w2c,   // [64,64] in x out
@@ -1882,7 +1918,10 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
                           int64_t E,
                           // HAS_W == 2 only
                           const float* __restrict__ fwW,   // [64,9]
-                          const float* __restrict__ fwmask) {  // [E] or null
+                          const float* __restrict__ fwmask,  // [E] or null
+                          // WIDX only: w is a [T,64] table, row r takes
+                          // w[widx[r]]
+                          const int32_t* __restrict__ widx = nullptr) {
     __shared__ float4 wlds[64 * 32];
     __shared__ float4 wl9[HAS_W == 2 ? 64 * RBF_PAD / 4 : 1];
     __shared__ float4 bst[HAS_W == 2 ? (BLOCK / 64) * RBF_TILE / 4 : 1];
@@ -1921,6 +1960,8 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
             alo[i] = ap[2 * i];
             ahi[i] = ap[16 + 2 * i];
         }
+        int wsv = 0;
+        if (WIDX) wsv = widx[lrow];
         __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
         float* st = (float*)bst + wave * RBF_TILE;
         if (HAS_W == 2) radial_tile_store(st, sv, lane_t);
@@ -1946,11 +1987,13 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
         }
         __builtin_amdgcn_s_setprio(0);
         if (base + 32 <= E)
-            mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, true>(
-                acc, bcol, w, bs, cout, gout, out, base, E, c, h, wl9, st4);
+            mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, true, WIDX>(
+                acc, bcol, w, bs, cout, gout, out, base, E, c, h, wl9, st4,
+                wsv);
         else
-            mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, false>(
-                acc, bcol, w, bs, cout, gout, out, base, E, c, h, wl9, st4);
+            mlp_tail_fwd_epilogue<KEEP, HAS_W, HAS_BASE, false, WIDX>(
+                acc, bcol, w, bs, cout, gout, out, base, E, c, h, wl9, st4,
+                wsv);
     }
 }
 
@@ -2001,6 +2044,15 @@ void k_gated_mlp_tail_fwd(const float* __restrict__ hp,    // [E,128]
 // The four factored-w variants <2, KEEP, true, 2, HAS_BASE>
 // (dm_gated_mlp3_fw_f32): 243-256 VGPR (256: no-keep with base), 0 AGPR,
 // 60-92 SGPR, 75264 B LDS, 2 waves/SIMD, no scratch.
+// The two indexed-w variants <3, KEEP, true, 1, false, true>
+// (dm_gated_mlp4_widx_f32; the lane loads widx[base + c] with the gate half's
+// gathers, an MFMA run ahead of the w loads it feeds): 256 VGPR, 0 AGPR, 56
+// (no-keep) / 88 (keep) SGPR, 66048 B LDS, 2 waves/SIMD, no scratch.  With
+// base the keep form spills (12 B of scratch), so neither form with base is
+// built and the entry refuses base.  All 22 other variants are unchanged.
+// These two sit AT the 256 registers of two waves per SIMD, with no headroom:
+// any edit to mlp_tail_fwd_loads or to the tile loop below is likely to make
+// them spill, so read the remarks for them first after such an edit.
 // 384-thread blocks (3 waves/SIMD) would need <= 168 VGPR, i.e. none of the
 // look-ahead; not built.
 // Stand-alone at 46M rows (tests/perf_gated_mlp_fused.py, median of 5, ms;
@@ -2099,7 +2151,8 @@ __device__ __forceinline__ void gated_mlp_interleave() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int NGATHER, bool KEEP, bool OUT, int HAS_W, bool HAS_BASE>
+template <int NGATHER, bool KEEP, bool OUT, int HAS_W, bool HAS_BASE,
+          bool WIDX = false>
 __global__ __launch_bounds__(256, 2)
 void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
                     const float* __restrict__ WT,    // [64,128] row-major
@@ -2124,7 +2177,9 @@ void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
                     int64_t E,
                     // HAS_W == 2 only
                     const float* __restrict__ fwW,   // [64,9]
-                    const float* __restrict__ fwmask) {  // [E] or null
+                    const float* __restrict__ fwmask,  // [E] or null
+                    // WIDX only: w is a [T,64] table, row r takes w[widx[r]]
+                    const int32_t* __restrict__ widx = nullptr) {
     // the two parents' LDS images, unchanged
     __shared__ float4 wl1[64 * 32];
     __shared__ float4 wl2[64 * 32];
@@ -2233,6 +2288,9 @@ void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
         // the gate half's gathers, then a[] and the indices are dead: the
         // next tile's (the last tile reloads its own, clamped as ever)
         gated_mlp_gather<NGATHER, 1>(gv, p0, p1, p2);
+        // the tile's w indices, an MFMA run ahead of the w loads they feed
+        int wsv = 0;
+        if (WIDX) wsv = widx[live ? r : E - 1];
         const int64_t next = tile + stride;
         const bool more = next < ntiles;
         load_tile(more ? next : tile, c, h);
@@ -2256,8 +2314,8 @@ void k_gated_mlp_64(const float* __restrict__ erow,  // [E,64]
         if (HAS_W == 2) radial_tile_load(sv, w, fwmask, base, E, lane_t);
         // (always the clamping form: a branch to the unclamped one on full
         // tiles spills, 96-344 B of scratch in six variants)
-        mlp_tail_fwd_loads<HAS_W, HAS_BASE, false, 16>(wv, bv, 0, w, bs, base,
-                                                       E, c, h);
+        mlp_tail_fwd_loads<HAS_W, HAS_BASE, false, 16, WIDX>(
+            wv, bv, 0, w, bs, base, E, c, h, wsv);
         __builtin_amdgcn_sched_barrier(0);
         // ---- second layer, g ---------------------------------------------
 #pragma unroll
@@ -2926,7 +2984,8 @@ static int gated_mlp_run(const float* erow, const float* WT, const float* bias,
                          float* g_out, float* out, int64_t E, int64_t Din,
                          int64_t d, hipStream_t s,
                          const float* fwW = nullptr,
-                         const float* fwmask = nullptr) {
+                         const float* fwmask = nullptr,
+                         const int32_t* widx = nullptr) {
     if (Din != 64 || d != 64) {
         g_err = "gated_mlp fused kernel is compiled for Din=64, d=64";
         return -1;
@@ -2964,8 +3023,30 @@ static int gated_mlp_run(const float* erow, const float* WT, const float* bias,
                 "bexp and out";
         return -1;
     }
+    // indexed w: the three-gather forms with w and out, without base (the
+    // keep form with base would spill: 12 B of scratch)
+    if (widx && (NGATHER != 3 || !w || !out || base)) {
+        g_err = "gated_mlp: w_idx goes with the three-gather forms that "
+                "have w and out and no base";
+        return -1;
+    }
     if (E <= 0) return 0;
     const int grid = gated_mlp_blocks(E);
+    if constexpr (NGATHER == 3) {
+        if (widx) {
+#define DM_GMLP_WIDX(KEEP)                                                   \
+            k_gated_mlp_64<3, KEEP, true, 1, false, true>                    \
+                <<<grid, BLOCK, 0, s>>>(                                     \
+                    erow, WT, bias, g0, g1, g2, i0, i1, i2, w2c, w2g, b2c,   \
+                    b2g, w, nullptr, z_out, c_out, g_out, out, E, nullptr,   \
+                    nullptr, widx)
+            if (z_out) DM_GMLP_WIDX(true);
+            else DM_GMLP_WIDX(false);
+#undef DM_GMLP_WIDX
+            DM_CHECK_LAUNCH();
+            return 0;
+        }
+    }
 #define DM_GMLP_LAUNCH(KEEP, OUT, HW, HB)                                    \
     k_gated_mlp_64<NGATHER, KEEP, OUT, HW, HB><<<grid, BLOCK, 0, s>>>(       \
         erow, WT, bias, g0, g1, g2, i0, i1, i2, w2c, w2g, b2c, b2g, w, base, \
@@ -3438,6 +3519,110 @@ int dm_gated_mlp4_f32(const float* arow, const float* WT, const float* bias,
     return gated_mlp_run<3>(arow, WT, bias, z1, z2, zv, lsrc, ldst, center,
                             w2c, w2g, b2c, b2g, w, base, z_out, c_out, g_out,
                             out, L, Din, d, (hipStream_t)stream);
+}
+
+int dm_gated_mlp4_widx_f32(const float* arow, const float* WT,
+                           const float* bias, const float* z1, const float* z2,
+                           const float* zv, const int32_t* lsrc,
+                           const int32_t* ldst, const int32_t* center,
+                           const float* w2c, const float* w2g,
+                           const float* b2c, const float* b2g, const float* w,
+                           const int32_t* w_idx, const float* base,
+                           float* z_out, float* c_out, float* g_out,
+                           float* out, int64_t L, int64_t Din, int64_t d,
+                           uint64_t stream) {
+    if (!w_idx) {
+        g_err = "gated_mlp4_widx: w_idx must be given";
+        return -1;
+    }
+    return gated_mlp_run<3>(arow, WT, bias, z1, z2, zv, lsrc, ldst, center,
+                            w2c, w2g, b2c, b2g, w, base, z_out, c_out, g_out,
+                            out, L, Din, d, (hipStream_t)stream, nullptr,
+                            nullptr, w_idx);
+}
+
+int dm_gated_mlp_tail_fwd_widx_f32(const float* h, const float* w2c,
+                                   const float* w2g, const float* b2c,
+                                   const float* b2g, const float* w,
+                                   const int32_t* w_idx, const float* base,
+                                   float* c_out, float* g_out, float* out,
+                                   int64_t E, int64_t d, uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64) {
+        g_err = "gated_mlp_tail_fwd fused kernel is compiled for d=64";
+        return -1;
+    }
+    if ((c_out == nullptr) != (g_out == nullptr)) {
+        g_err = "gated_mlp_tail_fwd: c_out and g_out must be given together";
+        return -1;
+    }
+    if (!w || !w_idx) {
+        g_err = "gated_mlp_tail_fwd_widx: w and w_idx must be given";
+        return -1;
+    }
+    if (E <= 0) return 0;
+#define DM_TAIL_FWD_WIDX(KEEP, HB)                                            \
+    k_gated_mlp_tail_fwd<KEEP, 1, HB, true>                                   \
+        <<<edge_mlp_blocks(E), BLOCK, 0, s>>>(                                \
+            h, w2c, w2g, b2c, b2g, w, base, c_out, g_out, out, E, nullptr,    \
+            nullptr, w_idx)
+    if (c_out && base) DM_TAIL_FWD_WIDX(true, true);
+    else if (c_out) DM_TAIL_FWD_WIDX(true, false);
+    else if (base) DM_TAIL_FWD_WIDX(false, true);
+    else DM_TAIL_FWD_WIDX(false, false);
+#undef DM_TAIL_FWD_WIDX
+    DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_gated_mlp_tail_bwd_widx_f32(const float* go, const int32_t* idx,
+                                   const float* c, const float* g,
+                                   const float* w, const int32_t* w_idx,
+                                   const float* z, const float* w2c,
+                                   const float* w2g, float* dz, float* dw,
+                                   const int32_t* seg, const int32_t* row_ptr,
+                                   float* sums, double* part, int64_t E,
+                                   int64_t N, int64_t d, uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (d != 64) {
+        g_err = "gated_mlp_tail_bwd fused kernel is compiled for d=64";
+        return -1;
+    }
+    if (!w || !w_idx || !dw) {
+        g_err = "gated_mlp_tail_bwd_widx: w, w_idx and dw must be given";
+        return -1;
+    }
+    if (seg ? (!row_ptr || !sums || !part) : (row_ptr || sums || part)) {
+        g_err = "gated_mlp_tail_bwd_widx: seg, row_ptr, sums and part must be "
+                "given together";
+        return -1;
+    }
+    if (E > 0) {
+        const int grid = edge_mlp_blocks(E);
+        if (seg && idx)
+            k_gated_mlp_tail_bwd_seg<1, true, true><<<grid, BLOCK, 0, s>>>(
+                go, idx, c, g, w, z, w2c, w2g, dz, dw, E, nullptr, nullptr,
+                nullptr, nullptr, seg, sums, part, w_idx);
+        else if (seg)
+            k_gated_mlp_tail_bwd_seg<1, false, true><<<grid, BLOCK, 0, s>>>(
+                go, nullptr, c, g, w, z, w2c, w2g, dz, dw, E, nullptr, nullptr,
+                nullptr, nullptr, seg, sums, part, w_idx);
+        else if (idx)
+            k_gated_mlp_tail_bwd<1, true, true><<<grid, BLOCK, 0, s>>>(
+                go, idx, c, g, w, z, w2c, w2g, dz, dw, E, nullptr, nullptr,
+                nullptr, nullptr, w_idx);
+        else
+            k_gated_mlp_tail_bwd<1, false, true><<<grid, BLOCK, 0, s>>>(
+                go, nullptr, c, g, w, z, w2c, w2g, dz, dw, E, nullptr, nullptr,
+                nullptr, nullptr, w_idx);
+        DM_CHECK_LAUNCH();
+    }
+    if (seg && N > 0) {
+        k_seg_fixup<<<nblocks(N, BLOCK / 32), BLOCK, 0, s>>>(
+            part, row_ptr, (float4*)sums, N, E);
+        DM_CHECK_LAUNCH();
+    }
+    return 0;
 }
 
 int dm_edge_geom_rbf_fwd_f32(const float* pos, const int32_t* src,

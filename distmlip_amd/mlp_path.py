@@ -17,6 +17,9 @@ that call each other:
     atom block         needs the fused first layer and no DM_FUSED_CONV
     lazy exchange      needs the row exchange, the atom block and the fused
                        first-layer reverse
+    line block         needs the atom block, the three-gather fused first
+                       layer, both fused tails with w_idx (the reverse one
+                       with go_idx too), and the fused first-layer reverse
 """
 from __future__ import annotations
 
@@ -117,6 +120,12 @@ def whole_mlp_act(ops, d) -> bool:
                       "mlp_tail_act")
 
 
+def whole_mlp4_keep(ops, d) -> bool:
+    """A three-gather MLP as the one kernel r_gated_mlp4 (keeps z and cg)."""
+    return _whole_mlp(ops, d, "r_gated_mlp4", "edge_mlp4_act",
+                      "r_mlp_tail_fwd")
+
+
 def factored_w(ops, d) -> bool:
     """The tail kernels take a block's message weights as factors
     (ops.RadialW) and the dense [E,d] arrays are never built."""
@@ -138,6 +147,14 @@ def fused_seg(ops, d) -> bool:
             and os.environ.get(NO_FUSED_SEG, "0") != "1")
 
 
+def line_seg(ops, d) -> bool:
+    """r_mlp_tail_bwd also returns the l_dst segment sums of dz for a dense w
+    with seg= (ops.LineSeg)."""
+    return (getattr(ops, "tail_bwd_seg", False) and getattr(ops, "w_idx", False)
+            and fused_tail_bwd(ops, d)
+            and os.environ.get(NO_FUSED_SEG, "0") != "1")
+
+
 # -- conv blocks and whole steps ---------------------------------------------
 
 def fused_keep_packs() -> bool:
@@ -154,6 +171,28 @@ def atom_block(ops, d) -> bool:
             and fused_first(ops, d, "r_edge_mlp3")
             and hasattr(ops, "r_edge_mlp_bwd")
             and hasattr(ops, "edge_mlp3_act"))
+
+
+# DM_NO_LINE_BLOCK=1: checkpointed steps keep torch.utils.checkpoint around
+# the op-by-op bond and angle blocks.  Read at call time like SWITCHES; it
+# turns no other predicate off.
+NO_LINE_BLOCK = "DM_NO_LINE_BLOCK"
+
+
+def line_block(ops, d) -> bool:
+    """Checkpointed steps run a bond or angle block as the self-recomputing
+    conv._BondBlockFn / _AngleBlockFn: the three-gather MLP (one kernel where
+    whole_mlp_act / whole_mlp4_keep allow, else the fused first layer + tail
+    pair, the same bits) with w3 read through l_src (w_idx), and the reverse
+    tail with go_idx, w_idx and the dense seg form."""
+    return (atom_block(ops, d)
+            and os.environ.get(NO_LINE_BLOCK, "0") != "1"
+            and fused_first(ops, d, "r_edge_mlp4")
+            and hasattr(ops, "edge_mlp4_act")
+            and fused_tail_fwd(ops, d) and fused_tail_fwd(ops, d, "mlp_tail_act")
+            and getattr(ops, "w_idx", False)
+            and getattr(ops, "tail_bwd_seg", False)
+            and indexed_tail_bwd(ops, d) and fused_first_bwd(ops, d))
 
 
 def final_keep() -> bool:

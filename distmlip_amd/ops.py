@@ -105,6 +105,19 @@ def hip_lib() -> ctypes.CDLL:
             fp, ip, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, ip,
             ip, fp, POINTER(ctypes.c_double), c_int64, c_int64, c_int64,
             c_int64, c_uint64]
+        # dense w read through a row index (w_idx)
+        lib.dm_gated_mlp_tail_fwd_widx_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_fwd_widx_f32.argtypes = [
+            fp, fp, fp, fp, fp, fp, ip, fp, fp, fp, fp, c_int64, c_int64,
+            c_uint64]
+        lib.dm_gated_mlp4_widx_f32.restype = c_int32
+        lib.dm_gated_mlp4_widx_f32.argtypes = [
+            fp, fp, fp, fp, fp, fp, ip, ip, ip, fp, fp, fp, fp, fp, ip, fp, fp,
+            fp, fp, fp, c_int64, c_int64, c_int64, c_uint64]
+        lib.dm_gated_mlp_tail_bwd_widx_f32.restype = c_int32
+        lib.dm_gated_mlp_tail_bwd_widx_f32.argtypes = [
+            fp, ip, fp, fp, fp, ip, fp, fp, fp, fp, fp, ip, ip, fp,
+            POINTER(ctypes.c_double), c_int64, c_int64, c_int64, c_uint64]
         lib.dm_mace_tp_fwd_f32.restype = c_int32
         lib.dm_mace_tp_fwd_f32.argtypes = [fp, fp, fp, fp, ip, fp, c_int32,
                                            fp, fp, fp, fp, c_int64, c_int32,
@@ -449,6 +462,20 @@ def raw_edge_mlp3(erow, wt, bias, zs, zd, src, dst, keep_z=True):
         _fp(erow), _fp(wt), _fp(bias), _fp(zs), _fp(zd), _ip(src), _ip(dst),
         _fp(z) if keep_z else None, _fp(h), E, wt.shape[0], dout, _stream()),
         "dm_edge_mlp3_f32")
+    return z, h
+
+
+def raw_edge_mlp4(arow, wt, bias, z1, z2, zv, pd):
+    """(z, silu(z)) with z = arow @ wt + bias + z1[l_src] + z2[l_dst] +
+    zv[center]: raw_edge_mlp3 over the line graph's three gathers."""
+    _chk_f32(arow, wt, bias, z1, z2, zv)
+    L, dout = arow.shape[0], wt.shape[1]
+    h = torch.empty(L, dout, dtype=arow.dtype, device=arow.device)
+    z = torch.empty_like(h)
+    _check(hip_lib().dm_edge_mlp4_f32(
+        _fp(arow), _fp(wt), _fp(bias), _fp(z1), _fp(z2), _fp(zv),
+        _ip(pd.l_src), _ip(pd.l_dst), _ip(pd.center), _fp(z), _fp(h), L,
+        wt.shape[0], dout, _stream()), "dm_edge_mlp4_f32")
     return z, h
 
 
@@ -812,7 +839,25 @@ def _split_w(w):
     return (None, w) if isinstance(w, RadialW) else (w, None)
 
 
-def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None):
+def _chk_w_idx(w, w_idx, E, d):
+    """w [T,d] dense with w_idx int32 [E]: row r of the kernel takes
+    w[w_idx[r]].  The range of w_idx is the caller's to guarantee (graph
+    indices), as for every gather index."""
+    assert w is not None and not isinstance(w, RadialW) \
+        and w.dim() == 2 and w.shape[1] == d and w.shape[0] > 0
+    assert w_idx.dtype == torch.int32 and w_idx.is_contiguous() \
+        and w_idx.device == w.device and w_idx.shape == (E,)
+
+
+class LineSeg:
+    """The line graph's dst-sorted rows as the seg of raw_mlp_tail_bwd."""
+
+    def __init__(self, pd):
+        self.dst, self.row_ptr, self.n_atoms = (pd.l_dst, pd.line_row_ptr,
+                                                pd.n_bonds)
+
+
+def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None, w_idx=None):
     """(dz, dw) of one gated MLP's tail in ONE kernel: the reverse of
     out = base + silu(cg[0]) * sigmoid(cg[1]) * w with cg = the second layer
     over silu(z).  go [E,d], cg [2,E,d] packed, w [E,d] or None, z [E,2d],
@@ -825,7 +870,10 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None):
     result, summed in the kernel's epilogue from the registers that hold dz
     and finished by a pass over per-tile fp64 partials: the bits of
     raw_seg_sum for a node whose rows lie within one 32-row tile, at most
-    1 ulp off for a node spread over several.  It needs a w."""
+    1 ulp off for a node spread over several.  It needs a w.
+    w_idx (int32 [E]): the dense w is a [T,d] table and row r takes
+    w[w_idx[r]]; dz and dw ([E,d], one row per r) are those of the
+    materialized w[w_idx]."""
     w, rw = _split_w(w)
     if rw is not None and seg is None:
         seg = rw.seg
@@ -833,7 +881,8 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None):
     d = go.shape[1]
     E = go.shape[0] if go_idx is None else go_idx.shape[0]
     assert cg.shape == (2, E, d) and z.shape == (E, 2 * d)
-    assert w2.shape == (2, d, d) and (w is None or w.shape == (E, d))
+    assert w2.shape == (2, d, d)
+    assert w_idx is not None or w is None or w.shape == (E, d)
     if go_idx is not None:
         assert go_idx.dtype == torch.int32 and go_idx.is_contiguous() \
             and go_idx.device == go.device
@@ -843,6 +892,26 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None):
         assert seg.dst.shape == (E,) and seg.dst.dtype == torch.int32 \
             and seg.row_ptr.dtype == torch.int32 \
             and seg.row_ptr.shape == (seg.n_atoms + 1,)
+    if w_idx is not None:
+        _chk_w_idx(w, w_idx, E, d)
+        dw = torch.empty(E, d, dtype=z.dtype, device=z.device)
+        sums = part = None
+        if seg is not None:
+            sums = torch.empty(seg.n_atoms, 2 * d, dtype=z.dtype,
+                               device=z.device)
+            part = torch.empty((E + 31) // 32, 2, 2 * d, dtype=torch.float64,
+                               device=z.device)
+        _check(lib.dm_gated_mlp_tail_bwd_widx_f32(
+            _fp(go), _ip(go_idx), *_halves(cg), _fp(w), _ip(w_idx), _fp(z),
+            *_halves(w2), _fp(dz), _fp(dw),
+            _ip(seg.dst) if seg is not None else None,
+            _ip(seg.row_ptr) if seg is not None else None, _fp(sums),
+            ctypes.cast(part.data_ptr(), POINTER(ctypes.c_double))
+            if part is not None else None, E,
+            seg.n_atoms if seg is not None else 0, d, _stream()),
+            "dm_gated_mlp_tail_bwd_widx_f32")
+        return (dz, dw, sums) if seg is not None else (dz, dw)
+    if seg is not None:
         acc = dw = dbexp = None
         if rw is not None:
             rw.check(E, d)
@@ -883,26 +952,32 @@ def raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx=None, seg=None):
     return dz, dw
 
 
-def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
+def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg, w_idx=None):
     """(out, cg or None) of one gated MLP's tail in ONE kernel:
     cg = baddbmm(b2, h halves, w2) and out = base + silu(cg[0]) *
     sigmoid(cg[1]) * w.  h [E,2d], w2 [2,d,d] (input x output per half),
     b2 [2,1,d], w and base [E,d] or None.  cg [2,E,d] packed is written and
     returned only with keep_cg; out is the same bit for bit either way.
-    d must be 64.  w may be a RadialW."""
+    d must be 64.  w may be a RadialW, or with w_idx (int32 [E]) a [T,d] table
+    of which row r takes w[w_idx[r]]."""
     w, rw = _split_w(w)
     _chk_f32(h, w2, b2, w, base)
     E, d = h.shape[0], w2.shape[1]
     assert h.shape == (E, 2 * d) and w2.shape == (2, d, d)
     assert b2.numel() == 2 * d
-    assert w is None or w.shape == (E, d)
+    assert w_idx is not None or w is None or w.shape == (E, d)
     assert base is None or base.shape == (E, d)
     out = torch.empty(E, d, dtype=h.dtype, device=h.device)
     cg = torch.empty(2, E, d, dtype=h.dtype, device=h.device) \
         if keep_cg else None
     head = (_fp(h), *_halves(w2), *_halves(b2))
     rest = (_fp(base), *_halves(cg), _fp(out), E, d)
-    if rw is not None:
+    if w_idx is not None:
+        _chk_w_idx(w, w_idx, E, d)
+        _check(hip_lib().dm_gated_mlp_tail_fwd_widx_f32(
+            *head, _fp(w), _ip(w_idx), *rest, _stream()),
+            "dm_gated_mlp_tail_fwd_widx_f32")
+    elif rw is not None:
         rw.check(E, d)
         _check(hip_lib().dm_gated_mlp_tail_fwd_fw_f32(
             *head, *rw.ptrs(), *rest, rw.bexp.shape[1], _stream()),
@@ -914,17 +989,18 @@ def raw_mlp_tail_fwd(h, w2, b2, w, base, keep_cg):
 
 
 def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
-                  want_out=True):
+                  want_out=True, w_idx=None):
     """One whole gated MLP in ONE kernel (dm_gated_mlp3/4_f32): the fused
     first layer over row [E,64] and 2 or 3 gathered tables, the second layer
     and the combine, without the h [E,128] array between them.  Returns
     (z, cg, out): z [E,128] and cg [2,E,64] packed with keep, else None; out
     None with want_out=False (keep only; w and base are then not read).
     Values are the two-kernel path's bit for bit.  w may be a RadialW (two
-    tables, with out)."""
+    tables, with out), or with w_idx (int32 [E]; three tables, with out, no
+    base) a [T,d] table of which row r takes w[w_idx[r]]."""
     w, rw = _split_w(w)
     if not want_out:
-        w = rw = base = None
+        w = rw = base = w_idx = None
     _chk_f32(row, wt, bias, *tables, w2, b2, w, base)
     E, d = row.shape[0], w2.shape[1]
     assert wt.shape == (d, 2 * d) and w2.shape == (2, d, d)
@@ -932,7 +1008,11 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
     assert len(tables) == len(idx) and len(tables) in (2, 3)
     assert all(t.shape[1] == 2 * d for t in tables)
     assert keep or want_out
-    assert w is None or w.shape == (E, d)
+    assert w_idx is not None or w is None or w.shape == (E, d)
+    if w_idx is not None:
+        assert len(tables) == 3 and base is None, \
+            "w_idx takes the three-gather form without base"
+        _chk_w_idx(w, w_idx, E, d)
     assert base is None or base.shape == (E, d)
     z = torch.empty(E, 2 * d, dtype=row.dtype, device=row.device) \
         if keep else None
@@ -946,7 +1026,11 @@ def raw_gated_mlp(row, wt, bias, tables, idx, w2, b2, w, base, keep,
     first = (_fp(row), _fp(wt), _fp(bias), *map(_fp, tables),
              *map(_ip, idx), *_halves(w2), *_halves(b2))
     rest = (_fp(base), _fp(z), *_halves(cg), _fp(out), E, wt.shape[0], d)
-    if rw is not None:
+    if w_idx is not None:
+        _check(hip_lib().dm_gated_mlp4_widx_f32(
+            *first, _fp(w), _ip(w_idx), *rest, _stream()),
+            "dm_gated_mlp4_widx_f32")
+    elif rw is not None:
         assert len(tables) == 2, "a factored w takes the two-gather form"
         rw.check(E, d)
         _check(hip_lib().dm_gated_mlp3_fw_f32(
@@ -1017,7 +1101,9 @@ class HipOps:
     is_reference = False
     tail_bwd_indexed = True      # r_mlp_tail_bwd takes go_idx
     factored_w = True            # the w of the MLP tails may be a RadialW
-    tail_bwd_seg = True          # ... and may carry a graph (with_seg)
+    tail_bwd_seg = True          # ... and may carry a graph (with_seg);
+                                 # a dense w takes seg= (ops.LineSeg)
+    w_idx = True                 # a dense w may be a table read by w_idx
 
     def gather(self, x, idx, csr=None):
         if csr is None:
@@ -1071,7 +1157,7 @@ class HipOps:
         return _GatedMlpTail.apply(
             z, h, w2, b2, _cont(w), _cont(base))
 
-    def mlp_tail_act(self, h, w2, b2, w=None, base=None):
+    def mlp_tail_act(self, h, w2, b2, w=None, base=None, w_idx=None):
         """mlp_tail's value for passes that record nothing (torch.no_grad
         inference, the lean recompute forwards of conv.py): out only, no cg is
         allocated or written.  Not differentiable: refused when an input
@@ -1081,9 +1167,10 @@ class HipOps:
             "mlp_tail_act is the no-grad form; use mlp_tail"
         if not isinstance(w, RadialW):
             w = _cont(w)
+        kw = {"w_idx": w_idx} if w_idx is not None else {}
         return raw_mlp_tail_fwd(
             h.contiguous(), w2, b2, w,
-            _cont(base), False)[0]
+            _cont(base), False, **kw)[0]
 
     def scatter_edges(self, msg, pd, base=None):
         return _SegSum.apply(msg, pd.dst, pd.row_ptr, pd.n_atoms, base)
@@ -1109,18 +1196,25 @@ class HipOps:
     def r_silu_bwd(self, go_h, z):
         return raw_silu_bwd(go_h.contiguous(), None, z)
 
-    def r_mlp_tail_bwd(self, go, cg, w, z, w2, go_idx=None):
+    def r_mlp_tail_bwd(self, go, cg, w, z, w2, go_idx=None, w_idx=None,
+                       seg=None):
         """(dz, dw): r_combine_bwd + second-layer reverse + r_silu_bwd in
         one kernel (d = 64 only).  go_idx: go is a node table read by index
         (r_gather_dst folded in).  With w a RadialW: (dz, dbexp), and with
-        one that carries a graph (with_seg): (dz, dbexp, r_seg_dst(dz))."""
-        return raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx)
+        one that carries a graph (with_seg): (dz, dbexp, r_seg_dst(dz)).
+        w_idx: the dense w is a table read by index (dw stays per row).
+        seg (dense w; LineSeg): the segment sums of dz as a third result."""
+        return raw_mlp_tail_bwd(go, cg, w, z, w2, go_idx, seg, w_idx)
 
     def r_edge_mlp3(self, erow, wt, bias, zs, zd, pd):
         """(z, h) of the fused first layer with z stored: r_gather_add3
         over addmm(bias, erow, wt) without that [E,2d] transient (wt =
         the [64,128] fusedT pack only)."""
         return raw_edge_mlp3(erow, wt, bias, zs, zd, pd.src, pd.dst)
+
+    def r_edge_mlp4(self, arow, wt, bias, z1, z2, zv, pd):
+        """r_edge_mlp3 over the line graph's three gathers."""
+        return raw_edge_mlp4(arow, wt, bias, z1, z2, zv, pd)
 
     # r_edge_mlp_bwd takes patch=(slot, rows)
     edge_mlp_bwd_patch = True
@@ -1140,25 +1234,37 @@ class HipOps:
         """dst[di] = 0 by rows, in place, one kernel."""
         return raw_zero_rows(dst, di)
 
-    def r_mlp_tail_fwd(self, h, w2, b2, w, base):
+    def r_mlp_tail_fwd(self, h, w2, b2, w, base, w_idx=None):
         """(cg, out): second layer + r_combine_fwd in one kernel (d = 64
-        only)."""
-        out, cg = raw_mlp_tail_fwd(h, w2, b2, w, base, True)
+        only).  w_idx: the dense w is a table read by index."""
+        kw = {"w_idx": w_idx} if w_idx is not None else {}
+        out, cg = raw_mlp_tail_fwd(h, w2, b2, w, base, True, **kw)
         return cg, out
 
     # whole gated MLP in one kernel (first layer, second layer, combine)
 
     def gated_mlp4_act(self, arow, wt, bias, z1, z2, zv, pd, w2, b2, w=None,
-                       base=None):
+                       base=None, w_idx=None):
         """mlp_tail_act(edge_mlp4_act(...), w2, b2, w, base) in one kernel,
-        h never reaching memory; for passes that record nothing."""
+        h never reaching memory; for passes that record nothing.  w_idx
+        (without base): w is a table read by index."""
         assert _no_grad_inputs(arow, z1, z2, zv, w, base), \
             "gated_mlp4_act is the no-grad form"
         return raw_gated_mlp(arow.contiguous(), wt, bias,
                              (z1.contiguous(), z2.contiguous(),
                               zv.contiguous()),
                              (pd.l_src, pd.l_dst, pd.center), w2, b2,
-                             _cont(w), _cont(base), False)[2]
+                             _cont(w), _cont(base), False, w_idx=w_idx)[2]
+
+    def r_gated_mlp4(self, arow, wt, bias, z1, z2, zv, pd, w2, b2, w, base,
+                     w_idx=None, want_out=True):
+        """(z, cg, out) of the fused three-gather first layer +
+        r_mlp_tail_fwd in one kernel, the keep form of gated_mlp4_act: same
+        out bit for bit; out is None with want_out=False, and w and base are
+        then not read."""
+        return raw_gated_mlp(arow, wt, bias, (z1, z2, zv),
+                             (pd.l_src, pd.l_dst, pd.center), w2, b2, w, base,
+                             True, want_out, w_idx)
 
     def r_gated_mlp3(self, erow, wt, bias, zs, zd, pd, w2, b2, w, base,
                      want_out=True):

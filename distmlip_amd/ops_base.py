@@ -104,12 +104,7 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             r_mlp_tail_fwd as one kernel, same
                                             values bit for bit; with
                                             want_out=False out is None and w,
-                                            base are not read.  OPTIONAL.  (The
-                                            keep form over three gathers
-                                            exists as the C entry
-                                            dm_gated_mlp4_f32 only: bond_fwd /
-                                            angle_fwd run their first layer
-                                            through rocBLAS)
+                                            base are not read.  OPTIONAL
     factored_w = True (class attribute)  -> OPTIONAL (n_rbf = 9): mlp_tail_act,
                                             r_mlp_tail_fwd, r_gated_mlp3 and
                                             r_mlp_tail_bwd take an ops.RadialW
@@ -125,6 +120,22 @@ the permutation CSRs the graph builder emits; `csr` is an optional
                                             r_seg_dst(dz, pd)), the sums from
                                             the kernel's epilogue (at most
                                             1 ulp from r_seg_dst's)
+    w_idx = True (class attribute)       -> OPTIONAL: gated_mlp4_act,
+                                            r_gated_mlp4 (both without base),
+                                            mlp_tail_act, r_mlp_tail_fwd and
+                                            r_mlp_tail_bwd take w_idx=int32
+                                            [E] with a dense w [T,d]: row r
+                                            uses w[w_idx[r]], the values on
+                                            the gathered array bit for bit; dw
+                                            stays [E,d].  r_mlp_tail_bwd then
+                                            also takes seg=ops.LineSeg(pd) and
+                                            returns r_seg_ldst(dz) third
+    r_edge_mlp4(a, wt, bias, z1, z2, zv, pd)
+                                         -> r_edge_mlp3 over the line graph's
+                                            three gathers.  OPTIONAL
+    r_gated_mlp4(a, wt, bias, z1, z2, zv, pd, w2, b2, w, base, w_idx=None,
+                 want_out=True)          -> r_gated_mlp3 over the line graph's
+                                            three gathers.  OPTIONAL
     r_gather_dst(x, pd)                  -> x[pd.dst]
     r_seg_dst(msg, pd, base)             -> segment-sum over the dst CSR
     r_seg_src(msg, pd)                   -> permuted segment-sum (src CSR)

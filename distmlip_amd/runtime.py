@@ -33,10 +33,11 @@ import torch
 import torch.distributed as dist
 
 from distmlip_amd import mlp_path
-from distmlip_amd.conv import (ExchangeHolder, _AtomBlockFn,
-                               _AtomBlockKeepFn, _AtomConvFn,
+from distmlip_amd.conv import (ExchangeHolder, _AngleBlockFn, _AtomBlockFn,
+                               _AtomBlockKeepFn, _AtomConvFn, _BondBlockFn,
                                _BondConvFn, atom_block_available,
-                               bond_to_edge, conv_fn_available, edge_to_bond)
+                               bond_to_edge, conv_fn_available, edge_to_bond,
+                               line_block_available)
 from distmlip_amd.chgnet import (
     PartitionData,
     _packed_weights,
@@ -628,7 +629,19 @@ class SpmdEngine:
                                            w=wl)
                     return ops.scatter_lines(msg, pd, base=n)
 
-                n = _ck(bond_body, n, a, v, exp3)
+                # checkpointed steps without a bond mask: the block
+                # recomputes itself, like the atom block
+                line_blk = False
+                if ckpt and bond_mask is None:
+                    W3 = core.threebody_bond_weights.weight
+                    pb = _packed_weights(blk.bond_mlp)
+                    line_blk = (not W3.requires_grad
+                                and line_block_available(ops, pb, d, ft))
+                if line_blk and (n.requires_grad or a.requires_grad
+                                 or v.requires_grad or exp3.requires_grad):
+                    n = _BondBlockFn.apply(n, a, v, exp3, W3, pd, ops, pb, d)
+                else:
+                    n = _ck(bond_body, n, a, v, exp3)
                 if row_x:
                     e = bond_to_edge(e, n, pd, ops, holder)
                 else:
@@ -645,7 +658,14 @@ class SpmdEngine:
                         return gated_mlp_split4(_blk.angle_mlp, n, a, v, pd,
                                                 ops, d, base=a)
 
-                    a = _ck(angle_body, n, a, v)
+                    pa = _packed_weights(blk.angle_mlp) if line_blk \
+                        else None
+                    if (line_blk and not pa[0].requires_grad
+                            and (n.requires_grad or a.requires_grad
+                                 or v.requires_grad)):
+                        a = _AngleBlockFn.apply(n, a, v, pd, ops, pa, d)
+                    else:
+                        a = _ck(angle_body, n, a, v)
             else:
                 v = _halo(v, plan)
 

@@ -300,6 +300,47 @@ int dm_gated_mlp_tail_bwd_seg_f32(const float* go, const int32_t* idx,
                                   int64_t N, int64_t d, int64_t n_rbf,
                                   uint64_t stream);
 
+/* Dense w read through a row index.  The three entries below are
+ * dm_gated_mlp_tail_fwd_f32, dm_gated_mlp4_f32 and dm_gated_mlp_tail_bwd_f32 /
+ * _idx_f32 / _seg_f32 with w a [T,d] table and w_idx [E] int32 (values in
+ * [0,T)): row r uses w[w_idx[r]].  Every output is the plain entry's on the
+ * materialized [E,d] array w[w_idx] bit for bit; that array is never built.
+ * dw stays one row per r, [E,d] (the sum over equal w_idx is the caller's).
+ * w and w_idx must be given.
+ *   dm_gated_mlp_tail_fwd_widx_f32  c_out/g_out both NULL or both given, base
+ *                                   may be NULL
+ *   dm_gated_mlp4_widx_f32          the no-keep form and the keep form with
+ *                                   out; base must be NULL
+ *   dm_gated_mlp_tail_bwd_widx_f32  idx may be NULL (plain go); seg, row_ptr,
+ *                                   sums and part all NULL (no segment sums)
+ *                                   or all given as in
+ *                                   dm_gated_mlp_tail_bwd_seg_f32
+ * Anything else returns an error and launches nothing. */
+int dm_gated_mlp_tail_fwd_widx_f32(const float* h, const float* w2c,
+                                   const float* w2g, const float* b2c,
+                                   const float* b2g, const float* w,
+                                   const int32_t* w_idx, const float* base,
+                                   float* c_out, float* g_out, float* out,
+                                   int64_t E, int64_t d, uint64_t stream);
+int dm_gated_mlp4_widx_f32(const float* arow, const float* WT,
+                           const float* bias, const float* z1, const float* z2,
+                           const float* zv, const int32_t* lsrc,
+                           const int32_t* ldst, const int32_t* center,
+                           const float* w2c, const float* w2g,
+                           const float* b2c, const float* b2g, const float* w,
+                           const int32_t* w_idx, const float* base,
+                           float* z_out, float* c_out, float* g_out,
+                           float* out, int64_t L, int64_t Din, int64_t d,
+                           uint64_t stream);
+int dm_gated_mlp_tail_bwd_widx_f32(const float* go, const int32_t* idx,
+                                   const float* c, const float* g,
+                                   const float* w, const int32_t* w_idx,
+                                   const float* z, const float* w2c,
+                                   const float* w2g, float* dz, float* dw,
+                                   const int32_t* seg, const int32_t* row_ptr,
+                                   float* sums, double* part, int64_t E,
+                                   int64_t N, int64_t d, uint64_t stream);
+
 /* Fused edge geometry + radial basis (replaces the torch chain for
  * chgnet.py:96-124): per local edge e,
  *   bv[e]  = pos[dst[e]] + offshift[e] - pos[src[e]]
