@@ -188,27 +188,32 @@ def atom_fwd(ops, pd, v, e, wbb, wab, packs_edge, packs_node, d,
     return v2, e2, (z1, cg1, z2, cg2)
 
 
-def _node_grad(ops, pd, go_v2, dzs, weights, sds=None):
+def _node_grad(ops, pd, go_v2, dzs, weights, sds=None, sss=None):
     """go_v2 + sum over the MLPs of seg_src(dz) @ ws + seg_dst(dz) @ wd: the
     v gradient of an atom conv, every term a fused addmm.  dzs (one dz per
     (ws, wd) of weights, None to skip) is emptied as it goes, so each dz is
     freed once consumed when the caller holds no other reference.  sds: per
     MLP, the list of what its reverse tail returned after (dz, dw): empty, or
-    seg_dst(dz) from that kernel's epilogue, used in place of r_seg_dst."""
+    seg_dst(dz) from that kernel's epilogue, used in place of r_seg_dst.
+    sss: per MLP, None or seg_src(dz) from r_edge_mlp_bwd_src, used in place
+    of r_seg_src; with both sums ready its dz may be True (already freed)."""
     gv = go_v2
     for i, (ws, wd) in enumerate(weights):
         dz = dzs.pop(0)
         sd = sds[i] if sds else ()
+        ss = sss[i] if sss else None
         if dz is None:
             continue
+        if ss is None:
+            ss = ops.r_seg_src(dz, pd)
         if gv is None:
-            gv = ops.r_seg_src(dz, pd) @ ws
+            gv = ss @ ws
         elif gv is go_v2:
-            gv = torch.addmm(go_v2, ops.r_seg_src(dz, pd), ws)
+            gv = torch.addmm(go_v2, ss, ws)
         else:
-            gv.addmm_(ops.r_seg_src(dz, pd), ws)
+            gv.addmm_(ss, ws)
         gv.addmm_(sd[0] if sd else ops.r_seg_dst(dz, pd), wd)
-        del dz
+        del dz, ss
     return gv
 
 
@@ -228,7 +233,10 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     node MLP's tail reads go_v2 by pd.dst instead of a gathered copy.
     saved may be a list: it is emptied, so each save is freed as soon as
     it is consumed.  need_gv=False skips the four segment sums and GEMMs
-    of the v gradient (gv is None) when v takes no gradient.
+    of the v gradient (gv is None) when v takes no gradient.  Where
+    mlp_path.fused_src_seg allows, the two first-layer reverses run as
+    r_edge_mlp_bwd_src and hand their seg_src(dz) to _node_grad; a dz whose
+    two sums are both made is dropped right there.
 
     patch ([B,d], from an ExchangeHolder): the rows pd.map_de of go_e2 are
     stale and stand for patch[pd.map_ude].  The node MLP's r_edge_mlp_bwd,
@@ -254,6 +262,9 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     # seg_dst(dz) as a third result, for _node_grad (sd1, sd2: [] without)
     if factored and need_gv and mlp_path.fused_seg(ops, d):
         wbb, wab = wbb.with_seg(pd), wab.with_seg(pd)
+    # the first layers' reverses also return seg_src(dz) (ss1, ss2)
+    src_seg = need_gv and mlp_path.fused_src_seg(ops, d)
+    ss1 = ss2 = None
 
     # node MLP reverse (v2 = v + seg_dst(msg))
     sd2 = []
@@ -268,7 +279,14 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
         del z2, cg2
         # e2 grad: external + the node MLP's per-edge GEMM, fused.  The
         # result is a fresh buffer, never go_e2 itself
-        if patch is not None:
+        if ft2 is not None and src_seg:
+            ge2, ss2 = ops.r_edge_mlp_bwd_src(
+                dz2, ft2, go_e2, pd,
+                patch=(slot_map(pd, go_e2.shape[0]), patch.contiguous())
+                if patch is not None else None)
+            if sd2:
+                dz2 = True      # both sums are made: dz2 is freed here
+        elif patch is not None:
             ge2 = ops.r_edge_mlp_bwd(
                 dz2, ft2, go_e2,
                 patch=(slot_map(pd, go_e2.shape[0]), patch.contiguous()))
@@ -293,7 +311,12 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     dz1, dwbb, *sd1 = _mlp_tail_bwd(ops, ge2, cg1, wbb, z1, w21, d)
     del z1, cg1
     # base passthrough + GEMM; in place only over the ge2 made above
-    if ft1 is not None:
+    if ft1 is not None and src_seg:
+        ge, ss1 = ops.r_edge_mlp_bwd_src(dz1, ft1, ge2, pd,
+                                         out=ge2 if owns_ge2 else None)
+        if sd1:
+            dz1 = True
+    elif ft1 is not None:
         ge = ops.r_edge_mlp_bwd(dz1, ft1, ge2,
                                 out=ge2 if owns_ge2 else None)
     else:
@@ -303,7 +326,7 @@ def atom_bwd(ops, pd, saved, packs_edge, packs_node, d, wbb, wab,
     del dz1, dz2
     # v grad: passthrough + all four per-node GEMM backs, fused
     gv = _node_grad(ops, pd, go_v2, dzs, ((ws1, wd1), (ws2, wd2)),
-                    (sd1, sd2)) if need_gv else None
+                    (sd1, sd2), (ss1, ss2)) if need_gv else None
     if acc_wbb is not None:
         acc_wbb.add_(dwbb)
         dwbb = None
@@ -434,14 +457,19 @@ def bond_bwd(ops, pd, saved, packs, d, go_n2, mask_l=None,
         dz, dwl = _mlp_tail_bwd(ops, dmsg, cg, wl, z, w2, d)
         del dmsg
     del z, cg, wl
+    ss = None       # r_seg_lsrc(dz) where the first layer's reverse made it
     if acc_a is not None:
         acc_a.addmm_(dz, wa)
         da = None
+    elif ft is not None and mlp_path.fused_src_seg(ops, d):
+        da, ss = ops.r_edge_mlp_bwd_src(dz, ft, None, pd, line=True)
     elif ft is not None:
         da = ops.r_edge_mlp_bwd(dz, ft)
     else:
         da = dz @ wa
-    gn = torch.addmm(go_n2, ops.r_seg_lsrc(dz, pd), w1)
+    gn = torch.addmm(go_n2, ss if ss is not None else ops.r_seg_lsrc(dz, pd),
+                     w1)
+    del ss
     gn.addmm_(sd[0] if sd else ops.r_seg_ldst(dz, pd), wn2)
     if acc_v is not None:
         acc_v.addmm_(ops.r_seg_center(dz, pd), wv)
@@ -482,15 +510,20 @@ def angle_bwd(ops, pd, saved, packs, d, go_a2, acc_n=None, acc_v=None):
     dz, _ = _mlp_tail_bwd(ops, go_a2, cg, None, z, w2, d)
     del z, cg
     # a fresh buffer, never go_a2 itself
-    da = ops.r_edge_mlp_bwd(dz, ft, go_a2) if ft is not None \
-        else torch.addmm(go_a2, dz, wa)
+    if ft is not None and mlp_path.fused_src_seg(ops, d):
+        da, ss = ops.r_edge_mlp_bwd_src(dz, ft, go_a2, pd, line=True)
+    else:
+        da = ops.r_edge_mlp_bwd(dz, ft, go_a2) if ft is not None \
+            else torch.addmm(go_a2, dz, wa)
+        ss = ops.r_seg_lsrc(dz, pd)
     if acc_n is not None:
         gn = None
-        acc_n.addmm_(ops.r_seg_lsrc(dz, pd), w1)
+        acc_n.addmm_(ss, w1)
         acc_n.addmm_(ops.r_seg_ldst(dz, pd), wn2)
     else:
-        gn = ops.r_seg_lsrc(dz, pd) @ w1
+        gn = ss @ w1
         gn.addmm_(ops.r_seg_ldst(dz, pd), wn2)
+    del ss
     if acc_v is not None:
         acc_v.addmm_(ops.r_seg_center(dz, pd), wv)
         gv = None

@@ -1670,6 +1670,216 @@ void k_edge_mlp_bwd(const float* __restrict__ dz,    // [E,128]
 }
 
 // ---------------------------------------------------------------------------
+// k_edge_mlp_bwd over the rows in src-sorted order, with the src segment sums
+// of dz formed while the tile is on chip (dm_edge_mlp_bwd_src_f32): position
+// k = 32 tile + c processes row perm[k], so a src node's rows are contiguous
+// positions, and sums[n] is what dm_seg_sum_gather_f32(dz, perm, row_ptr)
+// gives without that kernel's second read of dz from memory.
+//  * Row order: lane c loads perm[k] (clamped like every load) one tile
+//    ahead, so the A operand's addresses do not wait for it.  The kernel is
+//    row-independent, so out[row] has the bits of k_edge_mlp_bwd: same k
+//    order, one rounding of gbase + acc.  The epilogue takes the row of each
+//    accumulator register by v_readlane from that register (a compile-time
+//    lane number per half-wave) and reads gbase / writes out at that row;
+//    perm is a permutation, so tiles still own disjoint rows and out may be
+//    gbase.  PATCH: slot[row], loaded by the same lane, travels the same way.
+//  * Sums: the A layout (lane = row) is not what a column sum wants, so the
+//    tile is read a second time with lane = column: for each of its 32 rows
+//    (row index a scalar, by v_readlane) the wave loads the 512 contiguous
+//    bytes, lane (c, h) taking columns 64h + 2c and 64h + 2c + 1.  The loads
+//    are issued right behind the A loads of the same rows, so they are served
+//    on chip.  Each lane then adds its two columns in position order into
+//    fp64 with the segment ids as scalars, as seg_tile_sums does: a segment
+//    inside the tile is rounded once and stored to sums, the tile's first and
+//    last go to part[tile][0 / 1] and k_seg_fixup finishes them (and writes
+//    zeros for nodes without rows).  A node within one tile has the bits of
+//    k_seg_sum_gather_v4, a node over several tiles a reassociated fp64 sum.
+//  * Plain stores only, one writer per element of out, sums and part.
+//  * Tails: positions >= E load row perm[E-1] and store nothing; the sums
+//    walk stops at the tile's live rows.  All offsets are 64-bit.
+// Resources (hipcc -O3, gfx950, kernel-resource-usage remarks), <true>,
+// <false> and <true, true> alike: 161 VGPR (the A operand and the second
+// copy of the tile, 64 each, are live together), 0 AGPR, 47-55 SGPR, 32 KB
+// LDS, 3 waves/SIMD, no scratch.  3 waves/SIMD is what the grid cap of 3
+// blocks per CU gives the plain forms too.
+// ---------------------------------------------------------------------------
+template <bool HAS_BASE, bool FULL, bool PATCH>
+__device__ __forceinline__ void edge_mlp_bwd_src_epilogue(
+        const f32x16 (&acc)[2], const float* gbase, float* out, int64_t base,
+        int64_t E, int c, int h, int pv, int sv, const float* patch) {
+    constexpr int G = 8;
+#pragma unroll
+    for (int rb = 0; rb < 16; rb += G) {
+        float gv[G][2];
+        int64_t ro[G];
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            // row of position rl: lane rl holds it (clamped as its load is)
+            const int rl0 = (r & 3) + 8 * (r >> 2);
+            const int p0 = __builtin_amdgcn_readlane(pv, rl0);
+            const int p1 = __builtin_amdgcn_readlane(pv, rl0 + 4);
+            ro[t] = (int64_t)(h ? p1 : p0) * 64 + c;
+            if (HAS_BASE) {
+                const float* gp = gbase + ro[t];
+                if (PATCH) {
+                    const int s0 = __builtin_amdgcn_readlane(sv, rl0);
+                    const int s1 = __builtin_amdgcn_readlane(sv, rl0 + 4);
+                    const int sl = h ? s1 : s0;
+                    if (sl >= 0) gp = patch + (int64_t)sl * 64 + c;
+                }
+                gv[t][0] = gp[0];
+                gv[t][1] = gp[32];
+            }
+        }
+        if (HAS_BASE)
+            __builtin_amdgcn_sched_barrier(0);   // the batch in flight first
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            const int r = rb + t;
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (FULL || base + rl < E) {
+                float* op = out + ro[t];
+                op[0] = HAS_BASE ? gv[t][0] + acc[0][r] : acc[0][r];
+                op[32] = HAS_BASE ? gv[t][1] + acc[1][r] : acc[1][r];
+            }
+        }
+    }
+}
+
+// The walk of seg_tile_sums over a tile held as v[j] = (column col, col + 1)
+// of position j; n live positions, sv the segment id of the lane's position.
+template <bool FULL>
+__device__ __forceinline__ void seg_tile_sums_rows(
+        const float2 (&v)[32], int sv, int n, float* __restrict__ sums,
+        double* __restrict__ part, int64_t tile, int col) {
+    double a0 = 0.0, a1 = 0.0;
+    int cur = __builtin_amdgcn_readlane(sv, 0);
+    bool first = true;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        // (no break: the loop has to unroll, the rows are registers)
+        if (!FULL && j >= n) continue;
+        const int s = __builtin_amdgcn_readlane(sv, j);
+        if (j > 0 && s != cur) {
+            if (first)
+                *(double2*)(part + (tile * 2) * 128 + col) =
+                    make_double2(a0, a1);
+            else
+                *(float2*)(sums + (int64_t)cur * 128 + col) =
+                    make_float2((float)a0, (float)a1);
+            first = false;
+            cur = s;
+            a0 = a1 = 0.0;
+        }
+        a0 += (double)v[j].x;
+        a1 += (double)v[j].y;
+    }
+    *(double2*)(part + (tile * 2 + (first ? 0 : 1)) * 128 + col) =
+        make_double2(a0, a1);
+}
+
+template <bool HAS_BASE, bool PATCH = false>
+__global__ __launch_bounds__(256, 3)
+void k_edge_mlp_bwd_src(const float* __restrict__ dz,    // [E,128]
+                        const float* __restrict__ WT,    // [64,128] row-major
+                        const float* gbase,              // [E,64], HAS_BASE
+                        float* out,                      // [E,64], may be gbase
+                        int64_t E,
+                        const int32_t* __restrict__ perm,   // [E] row of a
+                                                            // position
+                        const int32_t* __restrict__ seg,    // [E] node of a
+                                                            // position
+                        float* __restrict__ sums,           // [N,128]
+                        double* __restrict__ part,          // [tiles,2,128]
+                        const int32_t* __restrict__ slot = nullptr,  // [E]
+                        const float* patch = nullptr) {  // [M,64], PATCH
+    static_assert(HAS_BASE || !PATCH, "a patch replaces rows of gbase");
+    __shared__ float2 wlds[128 * 32];
+    // i = (col, k) with k fastest: coalesced reads of the row-major WT
+    for (int i = threadIdx.x; i < 128 * 32; i += blockDim.x) {
+        const int k = i & 127, col = i >> 7;
+        wlds[k * 32 + col] = make_float2(WT[col * 128 + k],
+                                         WT[(32 + col) * 128 + k]);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+    const int64_t ntiles = (E + 31) >> 5;
+    const int64_t stride = (int64_t)gridDim.x * waves_per_block;
+    int64_t tile = blockIdx.x * (int64_t)waves_per_block + wave;
+    int pn = 0;
+    if (tile < ntiles) {
+        const int64_t k = (tile << 5) + (lane & 31);
+        pn = perm[k < E ? k : E - 1];
+    }
+    for (; tile < ntiles; tile += stride) {
+        const int64_t base = tile << 5;
+        // opaque copy per tile, as in k_edge_mlp_64x128: keeps the
+        // per-register row offsets from being hoisted and spilled
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int c = lane_t & 31, h = lane_t >> 5;
+        const float2* bl = wlds + (4 * h) * 32 + c;
+        const int64_t k = base + c;
+        const int64_t lk = k < E ? k : E - 1;   // clamp, never read past E
+        const int pv = pn;                      // row of position k
+        const float4* ap = (const float4*)(dz + (int64_t)pv * 128) + h;
+        float4 a[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = ap[2 * i];
+        // the tile again, lane = column pair, behind the loads of the same
+        // rows
+        float2 v[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const int pj = __builtin_amdgcn_readlane(pv, j);
+            v[j] = *((const float2*)(dz + (int64_t)pj * 128 + 64 * h) + c);
+        }
+        const int gv = seg[lk];
+        int sv = 0;
+        if (PATCH) sv = slot[pv];
+        {   // the next tile's rows, clamped the same way
+            const int64_t kn = k + (stride << 5);
+            pn = perm[kn < E ? kn : E - 1];
+        }
+        __builtin_amdgcn_sched_barrier(0);   // all loads in flight first
+        const int col = 64 * h + 2 * c;
+        if (base + 32 <= E)
+            seg_tile_sums_rows<true>(v, gv, 32, sums, part, tile, col);
+        else
+            seg_tile_sums_rows<false>(
+                v, gv, __builtin_amdgcn_readfirstlane((int)(E - base)), sums,
+                part, tile, col);
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc[2];
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[cb][q] = 0.0f;
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float2 b = bl[(8 * i + t) * 32];   // k = 8i + 4h + t
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b.y, acc[1], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        if (base + 32 <= E)
+            edge_mlp_bwd_src_epilogue<HAS_BASE, true, PATCH>(
+                acc, gbase, out, base, E, c, h, pv, sv, patch);
+        else
+            edge_mlp_bwd_src_epilogue<HAS_BASE, false, PATCH>(
+                acc, gbase, out, base, E, c, h, pv, sv, patch);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Fused forward tail of one gated MLP (d = 64): second layer + combine,
 //   c = h[:, :64] @ w2c + b2c      g = h[:, 64:] @ w2g + b2g
 //   out = base + silu(c) * sigmoid(g) * w
@@ -3410,6 +3620,51 @@ int dm_edge_mlp_bwd_patch_f32(const float* dz, const float* WT,
     k_edge_mlp_bwd<true, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
         dz, WT, gbase, out, E, slot, patch);
     DM_CHECK_LAUNCH();
+    return 0;
+}
+
+int dm_edge_mlp_bwd_src_f32(const float* dz, const float* WT,
+                            const float* gbase, const int32_t* slot,
+                            const float* patch, float* out,
+                            const int32_t* perm, const int32_t* seg,
+                            const int32_t* row_ptr, float* sums, double* part,
+                            int64_t E, int64_t N, int64_t Din, int64_t Dout,
+                            uint64_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (Din != 128 || Dout != 64) {
+        g_err = "edge_mlp_bwd fused kernel is compiled for Din=128, Dout=64";
+        return -1;
+    }
+    if (!out || !perm || !seg || !row_ptr || !sums || !part) {
+        g_err = "edge_mlp_bwd_src: out, perm, seg, row_ptr, sums and part "
+                "must be given";
+        return -1;
+    }
+    if (slot && !gbase) {
+        g_err = "edge_mlp_bwd_src: a patch replaces rows of gbase";
+        return -1;
+    }
+    if (slot && patch == out) {
+        g_err = "edge_mlp_bwd_src: patch must not be out";
+        return -1;
+    }
+    if (E > 0) {
+        if (slot)
+            k_edge_mlp_bwd_src<true, true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+                dz, WT, gbase, out, E, perm, seg, sums, part, slot, patch);
+        else if (gbase)
+            k_edge_mlp_bwd_src<true><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+                dz, WT, gbase, out, E, perm, seg, sums, part);
+        else
+            k_edge_mlp_bwd_src<false><<<edge_mlp_blocks(E), BLOCK, 0, s>>>(
+                dz, WT, nullptr, out, E, perm, seg, sums, part);
+        DM_CHECK_LAUNCH();
+    }
+    if (N > 0) {
+        k_seg_fixup<<<nblocks(N, BLOCK / 32), BLOCK, 0, s>>>(
+            part, row_ptr, (float4*)sums, N, E);
+        DM_CHECK_LAUNCH();
+    }
     return 0;
 }
 

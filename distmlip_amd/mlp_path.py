@@ -155,6 +155,19 @@ def line_seg(ops, d) -> bool:
             and os.environ.get(NO_FUSED_SEG, "0") != "1")
 
 
+# DM_NO_FUSED_SRC_SEG=1: the src segment sums of dz come from r_seg_src /
+# r_seg_lsrc launches instead of the first layer's reverse kernel.  Read at
+# call time like SWITCHES; it turns no other predicate off.
+NO_FUSED_SRC_SEG = "DM_NO_FUSED_SRC_SEG"
+
+
+def fused_src_seg(ops, d) -> bool:
+    """The first layer's reverse runs as r_edge_mlp_bwd_src, which walks the
+    rows in src order and also returns the src segment sums of dz."""
+    return (_can(ops, d, "r_edge_mlp_bwd_src") and fused_first_bwd(ops, d)
+            and os.environ.get(NO_FUSED_SRC_SEG, "0") != "1")
+
+
 # -- conv blocks and whole steps ---------------------------------------------
 
 def fused_keep_packs() -> bool:

@@ -73,6 +73,10 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_edge_mlp_bwd_patch_f32.argtypes = [fp, fp, fp, ip, fp, fp,
                                                   c_int64, c_int64, c_int64,
                                                   c_uint64]
+        lib.dm_edge_mlp_bwd_src_f32.restype = c_int32
+        lib.dm_edge_mlp_bwd_src_f32.argtypes = [
+            fp, fp, fp, ip, fp, fp, ip, ip, ip, fp, POINTER(ctypes.c_double),
+            c_int64, c_int64, c_int64, c_int64, c_uint64]
         lib.dm_gated_mlp_tail_fwd_f32.restype = c_int32
         lib.dm_gated_mlp_tail_fwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp,
                                                   fp, fp, fp, c_int64,
@@ -544,6 +548,61 @@ def raw_edge_mlp_bwd(dz, wt, gbase=None, out=None, patch=None):
         _fp(dz), _fp(wt), _fp(gbase), _fp(out), E, dz.shape[1], wt.shape[0],
         _stream()), "dm_edge_mlp_bwd_f32")
     return out
+
+
+def raw_edge_mlp_bwd_src(dz, wt, perm, seg, row_ptr, gbase=None, out=None,
+                         patch=None):
+    """(raw_edge_mlp_bwd(dz, wt, gbase, out, patch),
+    raw_seg_sum_gather(dz, perm, row_ptr, N)) from ONE read of dz: the kernel
+    walks the rows in the sorted order perm and sums each node's rows while
+    their tile is on chip.  seg int32 [E] is the node of each sorted position
+    (the sorted index itself, index[perm]); row_ptr int32 [N+1].  out has the
+    bits of raw_edge_mlp_bwd; the sums have those of raw_seg_sum_gather for a
+    node whose positions lie within one 32-row tile and are at most 1 ulp off
+    for a node spread over several (fp64 pieces added in tile order)."""
+    _chk_f32(dz, wt, gbase, out)
+    E = dz.shape[0]
+    N = row_ptr.shape[0] - 1
+    assert dz.shape[1] == wt.shape[1]
+    assert gbase is None or gbase.shape == (E, wt.shape[0])
+    for t in (perm, seg):
+        assert t.dtype == torch.int32 and t.is_contiguous() \
+            and t.device == dz.device and t.shape == (E,)
+    assert row_ptr.dtype == torch.int32 and row_ptr.is_contiguous() \
+        and row_ptr.device == dz.device
+    if out is None:
+        out = torch.empty(E, wt.shape[0], dtype=dz.dtype, device=dz.device)
+    assert out.shape == (E, wt.shape[0])
+    slot = rows = None
+    if patch is not None:
+        slot, rows = patch
+        _chk_f32(rows)
+        assert gbase is not None, "a patch replaces rows of gbase"
+        assert slot.dtype == torch.int32 and slot.is_contiguous() \
+            and slot.device == dz.device and slot.shape == (E,)
+        assert rows.dim() == 2 and rows.shape[1] == wt.shape[0]
+        assert (rows.untyped_storage().data_ptr()
+                != out.untyped_storage().data_ptr()), \
+            "patch rows must not alias out"
+    sums = torch.empty(N, dz.shape[1], dtype=dz.dtype, device=dz.device)
+    part = torch.empty(max((E + 31) // 32, 1), 2, dz.shape[1],
+                       dtype=torch.float64, device=dz.device)
+    _check(hip_lib().dm_edge_mlp_bwd_src_f32(
+        _fp(dz), _fp(wt), _fp(gbase), _ip(slot), _fp(rows), _fp(out),
+        _ip(perm), _ip(seg), _ip(row_ptr), _fp(sums),
+        ctypes.cast(part.data_ptr(), POINTER(ctypes.c_double)), E, N,
+        dz.shape[1], wt.shape[0], _stream()), "dm_edge_mlp_bwd_src_f32")
+    return out, sums
+
+
+def _sorted_index(pd, name, index, perm):
+    """index[perm] as int32, the node of each sorted position, kept on the
+    graph: it changes only when perm does."""
+    hit = getattr(pd, name, None)
+    if hit is None or hit[0] is not perm:
+        hit = (perm, index[perm.long()].to(torch.int32).contiguous())
+        setattr(pd, name, hit)
+    return hit[1]
 
 
 def _first_layer_de(dz, wt):
@@ -1219,11 +1278,30 @@ class HipOps:
     # r_edge_mlp_bwd takes patch=(slot, rows)
     edge_mlp_bwd_patch = True
 
-    def r_edge_mlp_bwd(self, dz, wt, gbase=None, out=None, patch=None):
+    def r_edge_mlp_bwd(self, dz, wt, gbase=None, out=None, patch=None,
+                       src=None):
         """(gbase +) dz @ wt.t() in one kernel (wt = the [64,128] fusedT
         pack only); out may be gbase when the caller owns it.  patch =
-        (slot, rows): gbase row r is rows[slot[r]] where slot[r] >= 0."""
+        (slot, rows): gbase row r is rows[slot[r]] where slot[r] >= 0.
+        src = (perm, seg, row_ptr), from r_edge_mlp_bwd_src: the pair
+        raw_edge_mlp_bwd_src returns."""
+        if src is not None:
+            return raw_edge_mlp_bwd_src(dz, wt, *src, gbase, out, patch)
         return raw_edge_mlp_bwd(dz, wt, gbase, out, patch)
+
+    def r_edge_mlp_bwd_src(self, dz, wt, gbase, pd, out=None, patch=None,
+                           line=False):
+        """(r_edge_mlp_bwd(dz, wt, gbase, out, patch), r_seg_src(dz, pd)) in
+        one kernel that reads dz once; line=True: r_seg_lsrc(dz, pd).  It is
+        a launch of r_edge_mlp_bwd, and goes through it."""
+        if line:
+            perm, rp = pd.line_src_perm, pd.line_src_row_ptr
+            seg = _sorted_index(pd, "_line_src_seg", pd.l_src, perm)
+        else:
+            perm, rp = pd.src_perm, pd.src_row_ptr
+            seg = _sorted_index(pd, "_src_seg", pd.src, perm)
+        return self.r_edge_mlp_bwd(dz, wt, gbase, out, patch=patch,
+                                   src=(perm, seg, rp))
 
     def r_move_rows(self, src, si, dst, di, add=False):
         """dst[di] (=|+=) src[si] by rows, in place over dst, one kernel;

@@ -176,6 +176,27 @@ int dm_edge_mlp_bwd_patch_f32(const float* dz, const float* WT,
                               const float* patch, float* out, int64_t E,
                               int64_t Din, int64_t Dout, uint64_t stream);
 
+/* dm_edge_mlp_bwd_f32 (slot NULL) or dm_edge_mlp_bwd_patch_f32 (slot given)
+ * that also returns the permuted segment sums of dz:
+ *   sums = dm_seg_sum_gather_f32(dz, perm, row_ptr, NULL, ., N, Din)
+ * from one read of dz.  perm int32 [E] is a permutation of the rows that
+ * sorts them by node, seg int32 [E] the node of each sorted position
+ * (non-decreasing, seg[k] = n for row_ptr[n] <= k < row_ptr[n+1]), row_ptr
+ * int32 [N+1]; none of them is checked.  out has the bits of the plain entry.
+ * sums [N,Din]: a node whose positions lie within one group of 32 has the
+ * bits of dm_seg_sum_gather_f32, any other a reassociated fp64 sum rounded
+ * once; a node without rows gets 0.  part is scratch, ceil(E/32)*2*Din
+ * doubles.  out may be gbase; it must not overlap dz, patch or sums.
+ * Same refusals as the plain entries; out, perm, seg, row_ptr, sums and part
+ * must not be NULL.  E <= 0 writes zeros to sums. */
+int dm_edge_mlp_bwd_src_f32(const float* dz, const float* WT,
+                            const float* gbase, const int32_t* slot,
+                            const float* patch, float* out,
+                            const int32_t* perm, const int32_t* seg,
+                            const int32_t* row_ptr, float* sums, double* part,
+                            int64_t E, int64_t N, int64_t Din, int64_t Dout,
+                            uint64_t stream);
+
 /* Fused forward tail of one gated MLP: the second layer over h [E,2d] and
  * the combine, in one kernel:
  *   c = h[:, :d] @ w2c + b2c        g = h[:, d:] @ w2g + b2g
