@@ -405,6 +405,118 @@ def conv_tp_hip(inter: Interaction, x0: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# fused HIP convolution: gather + uvu TP + dst sum in one kernel per pass,
+# one wave per (node, 64-channel block) — csrc/mace_conv.hip.  No per-edge
+# [E, *, C] array besides tp_w and its gradient.
+# ---------------------------------------------------------------------------
+
+def _conv_path_lists():
+    from distmlip_amd.mace_model import tp_paths
+    return (tuple(tp_paths((0,), 3)), tuple(tp_paths((0, 1), 3)))
+
+
+@lru_cache(maxsize=None)
+def _conv_K(paths_key, device_str):
+    """K [T,16]: row t = (p, k1, k3) holds CG_p[k1, :, k3] at the columns
+    of path p's l2 block, so yc[e,t] = sum_k2 K[t,k2] Y[e,k2]."""
+    rows = []
+    for (l1, l2, l3) in paths_key:
+        CG = so3.real_cg(l1, l2, l3)
+        o2, d2 = so3.L_OFF[l2], so3.L_DIMS[l2]
+        for k1 in range(CG.shape[0]):
+            for k3 in range(CG.shape[2]):
+                row = np.zeros(16)
+                row[o2:o2 + d2] = CG[k1, :, k3]
+                rows.append(row)
+    return torch.tensor(np.asarray(rows, dtype=np.float32),
+                        device=torch.device(device_str))
+
+
+class _MaceConvFn(torch.autograd.Function):
+    """M [N,16,C] = sum over in-edges of the uvu product of xs[src] [N,R,C],
+    Y [E,16], tp_w [E,P,C].  Forward one kernel over the dst CSR; backward
+    one kernel per CSR (dw and dY over dst, dxs over the src permutation).
+    Deterministic: no atomics."""
+
+    @staticmethod
+    def forward(ctx, xs, Y, tp_w, K, ls, src, dst, row_ptr, src_perm,
+                src_row_ptr):
+        from distmlip_amd.ops import _check, _chk_f32, _fp, _ip, _stream, \
+            hip_lib
+        _chk_f32(xs, Y, tp_w, K)
+        N, _, C = xs.shape
+        ctx.save_for_backward(xs, Y, tp_w)
+        ctx.idx = (K, ls, src, dst, row_ptr, src_perm, src_row_ptr)
+        if Y.shape[0] == 0:
+            return xs.new_zeros(N, 16, C)
+        M = torch.empty(N, 16, C, dtype=xs.dtype, device=xs.device)
+        _check(hip_lib().dm_mace_conv_fwd_f32(
+            _fp(xs), _fp(tp_w), _fp(Y), _fp(K), _ip(src), _ip(row_ptr),
+            _fp(M), N, C, ls, _stream()), "dm_mace_conv_fwd_f32")
+        return M
+
+    @staticmethod
+    def backward(ctx, G):
+        from distmlip_amd.ops import _check, _fp, _ip, _stream, hip_lib
+        xs, Y, tp_w = ctx.saved_tensors
+        K, ls, src, dst, row_ptr, src_perm, src_row_ptr = ctx.idx
+        N, _, C = xs.shape
+        E = Y.shape[0]
+        dxs = dY = dw = None
+        if E == 0:
+            return (torch.zeros_like(xs), torch.zeros_like(Y),
+                    torch.zeros_like(tp_w)) + (None,) * 7
+        G = G.contiguous()
+        if ctx.needs_input_grad[0]:
+            dxs = torch.empty_like(xs)
+            _check(hip_lib().dm_mace_conv_bwd_node_f32(
+                _fp(G), _fp(tp_w), _fp(Y), _fp(K), _ip(dst), _ip(src_perm),
+                _ip(src_row_ptr), _fp(dxs), N, C, ls, _stream()),
+                "dm_mace_conv_bwd_node_f32")
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw = torch.empty_like(tp_w)
+            dYp = torch.empty(C // 64, E, 16, dtype=Y.dtype, device=Y.device)
+            _check(hip_lib().dm_mace_conv_bwd_edge_f32(
+                _fp(G), _fp(xs), _fp(tp_w), _fp(Y), _fp(K), _ip(src),
+                _ip(row_ptr), _fp(dw), _fp(dYp), N, E, C, ls, _stream()),
+                "dm_mace_conv_bwd_edge_f32")
+            dY = dYp[0] if C == 64 else dYp.sum(0)
+        return (dxs, dY, dw) + (None,) * 7
+
+
+def conv_fused_available(inter: Interaction, Y: torch.Tensor, C: int, pd,
+                         ops) -> bool:
+    """DM_MACE_CONV=split pins the gather + conv_tp_hip + scatter path."""
+    import os
+    return (os.environ.get("DM_MACE_CONV", "fused") == "fused"
+            and os.environ.get("DM_MACE_TP", "hip") == "hip"
+            and Y.is_cuda and Y.dtype == torch.float32
+            and C % 64 == 0
+            and tuple(inter.paths) in _conv_path_lists()
+            and hasattr(pd, "src_perm")
+            and not getattr(ops, "is_reference", False))
+
+
+def conv_fused_hip(inter: Interaction, x_up: Dict[int, torch.Tensor],
+                   Y: torch.Tensor, tp_w: torch.Tensor, pd
+                   ) -> Dict[int, torch.Tensor]:
+    """Summed messages {l3: [N, C, 2*l3+1]} straight from the node blocks
+    x_up {l: [N, C, 2l+1]} (see _MaceConvFn); pd carries the int32 dst CSR
+    and src permutation CSR of the graph builder."""
+    paths_key = tuple(inter.paths)
+    ls = _conv_path_lists().index(paths_key)
+    K = _conv_K(paths_key, str(Y.device))
+    xs = torch.cat([x_up[l].permute(0, 2, 1) for l in sorted(x_up)],
+                   dim=1).contiguous()              # [N, R, C]
+    assert xs.shape[1] == (1, 4)[ls], xs.shape
+    M = _MaceConvFn.apply(xs, Y.contiguous(), tp_w.contiguous(), K, ls,
+                          pd.src, pd.dst, pd.row_ptr, pd.src_perm,
+                          pd.src_row_ptr)
+    return {l3: M[:, so3.L_OFF[l3]:so3.L_OFF[l3] + so3.L_DIMS[l3], :]
+            .permute(0, 2, 1).contiguous() for l3 in range(4)}
+
+
+# ---------------------------------------------------------------------------
 # fused HIP symmetric contraction (round 2): one wave per node, polynomial
 # entries via the scalar cache, x rows + accumulators in LDS.  Weights are
 # FROZEN (inference engine) — backward produces dx only, so the

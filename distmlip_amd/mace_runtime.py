@@ -193,6 +193,9 @@ class MaceSpmdEngine:
                 use_hip = mace_ops.conv_tp_hip_available(_inter, Y, C)
                 E_tot = len(pd.src)
                 if E_tot > chunk_e:
+                    # this branch stays on the per-edge kernels: the fused
+                    # convolution walks the src CSR in its reverse pass, and
+                    # a node-range chunk has no src CSR of its own
                     # node-range-chunked message pass (the uma_runtime
                     # pattern): per-edge transients ([E,P,C] radial
                     # weights + 4 [E,d3,C] TP outputs) reach ~40 GB per
@@ -258,6 +261,12 @@ class MaceSpmdEngine:
                         for i, l3 in enumerate(l3s):
                             cat = torch.cat([p_[i] for p_ in parts], 0)
                             m[l3] = cat.view(-1, C, 2 * l3 + 1)
+                elif mace_ops.conv_fused_available(_inter, Y, C, pd, ops):
+                    # gather + TP + dst sum in one kernel per pass
+                    # (csrc/mace_conv.hip): no [E, *, C] array but tp_w
+                    tp_w = _inter.radial(edge_feats).view(
+                        -1, len(_inter.paths), C)
+                    m = mace_ops.conv_fused_hip(_inter, x_up, Y, tp_w, pd)
                 elif use_hip:
                     tp_w = _inter.radial(edge_feats).view(
                         -1, len(_inter.paths), C)

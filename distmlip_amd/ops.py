@@ -173,6 +173,19 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_tn_msg_bwd_node_f32.restype = c_int32
         lib.dm_tn_msg_bwd_node_f32.argtypes = [fp, fp, ip, ip, ip, fp,
                                                c_int64, c_int32, c_uint64]
+        # MACE fused convolution (distmlip_amd/mace_ops.py, csrc/mace_conv.hip)
+        lib.dm_mace_conv_fwd_f32.restype = c_int32
+        lib.dm_mace_conv_fwd_f32.argtypes = [fp, fp, fp, fp, ip, ip, fp,
+                                             c_int64, c_int32, c_int32,
+                                             c_uint64]
+        lib.dm_mace_conv_bwd_edge_f32.restype = c_int32
+        lib.dm_mace_conv_bwd_edge_f32.argtypes = [fp, fp, fp, fp, fp, ip, ip,
+                                                  fp, fp, c_int64, c_int64,
+                                                  c_int32, c_int32, c_uint64]
+        lib.dm_mace_conv_bwd_node_f32.restype = c_int32
+        lib.dm_mace_conv_bwd_node_f32.argtypes = [fp, fp, fp, fp, ip, ip, ip,
+                                                  fp, c_int64, c_int32,
+                                                  c_int32, c_uint64]
         cf = ctypes.c_float
         lib.dm_edge_geom_rbf_fwd_f32.restype = c_int32
         lib.dm_edge_geom_rbf_fwd_f32.argtypes = [fp, ip, ip, fp, fp, cf,

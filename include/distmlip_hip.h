@@ -575,6 +575,52 @@ int dm_tn_msg_bwd_node_f32(const float* G, const float* f, const int32_t* dst,
                            const int32_t* src_row_ptr, float* dY, int64_t N,
                            int32_t C, uint64_t stream);
 
+/* MACE interaction convolution, fused per node (csrc/mace_conv.hip): the
+ * gather of sender rows, the uvu tensor product of dm_mace_tp_* and the sum
+ * per dst node in one pass, with no per-edge array besides Y, w, dY and dw.
+ * ls selects the path list: 0 = the 4 paths of an l = 0 sender (R = 1 row
+ * per node, T = 16), 1 = the 10 paths of an l = 0, 1 sender (R = 4, T = 88),
+ * both with l_max = 3, in mace_model.tp_paths order.  xs [N,R,C] holds the
+ * sender rows l-major, M and G = dL/dM are [N,16,C] with row l3*l3 + m3,
+ * w [E,P,C], Y [E,16].  K [T,16] is the coupling matrix: row t = (p, k1, k3)
+ * (path-major, then k1, then k3) holds CG_p[k1, :, k3] at the columns of p's
+ * l2 block, so yc[e,t] = sum_k2 K[t,k2] Y[e,k2].  Edges are DST-SORTED:
+ * row_ptr [N+1] is the dst CSR, (src_perm, src_row_ptr) the src permutation
+ * CSR.
+ *
+ *   fwd:      M[i,o3+k3,c]  = sum_{e in row i} sum_p w[e,p,c]
+ *                             sum_k1 xs[src[e],o1+k1,c] yc[e,(p,k1,k3)]
+ *   bwd_edge: dw[e,p,c]     = sum_{k1,k3} yc[e,t] xs[src[e],o1+k1,c]
+ *                             G[dst(e),o3+k3,c]
+ *             dYp[b,e,k2]   = sum_t K[t,k2] sum_{c in block b} w[e,p,c]
+ *                             xs[src[e],o1+k1,c] G[dst(e),o3+k3,c]
+ *             one [E,16] slice per 64-channel block b: dY is their sum
+ *   bwd_node: dxs[s,o1+k1,c] = sum_{j in src row s} sum_{p,k3} w[e,p,c]
+ *                             yc[e,t] G[dst[e],o3+k3,c],  e = src_perm[j]
+ *
+ * One wave per (node, 64-channel block), lane = channel, accumulators in
+ * registers, rows summed in CSR order, channel sums by a fixed butterfly:
+ * no atomics, results bit-identical from run to run.  A row without edges
+ * writes zeros (fwd, bwd_node).  N == 0 (and E == 0 for bwd_edge) returns 0
+ * with no launch.  C must be a positive multiple of 64 and ls 0 or 1:
+ * anything else returns nonzero and launches nothing. */
+int dm_mace_conv_fwd_f32(const float* xs, const float* tp_w, const float* Y,
+                         const float* K, const int32_t* src,
+                         const int32_t* row_ptr, float* M, int64_t N,
+                         int32_t C, int32_t ls, uint64_t stream);
+int dm_mace_conv_bwd_edge_f32(const float* G, const float* xs,
+                              const float* tp_w, const float* Y,
+                              const float* K, const int32_t* src,
+                              const int32_t* row_ptr, float* dw, float* dYp,
+                              int64_t N, int64_t E, int32_t C, int32_t ls,
+                              uint64_t stream);
+int dm_mace_conv_bwd_node_f32(const float* G, const float* tp_w,
+                              const float* Y, const float* K,
+                              const int32_t* dst, const int32_t* src_perm,
+                              const int32_t* src_row_ptr, float* dxs,
+                              int64_t N, int32_t C, int32_t ls,
+                              uint64_t stream);
+
 /* Integrator kernels of the native MD / relaxation driver
  * (distmlip_amd/md.py; the reference drives ASE's integrators instead,
  * implementations/matgl/ase.py:130-490).  State is fp64: wrapped fractional
