@@ -428,6 +428,339 @@ void k_mace_conv_bwd_edge(
     }
 }
 
+// ---------------------------------------------------------------------------
+// The same three passes with the radial MLP's last layer inside:
+//     w[e,p,c] = sum_j h[e,j] Wr[p C + c, j],      h [E,64], Wr [P C, 64]
+// is formed per tile of ETILE = 16 edges and per path on
+// v_mfma_f32_16x16x4_f32 and never reaches global memory; neither does dw,
+// which bwd_edge multiplies by Wr on the same instruction into
+//     dh[e,j] = sum_{p,c} dw[e,p,c] Wr[p C + c, j].
+//
+// A wave still owns one (node, 64-channel block) and walks its CSR row, now
+// sixteen edges at a time.  Per tile it loads the sixteen h rows once as the
+// A operand (lane = (edge i, k-quarter q), 16 registers) and writes the
+// sixteen yc rows to its stripe.  Then per path: four 16x16 tiles over
+// K = 64 (16 MFMAs each) give w[16 edges][64 channels], dropped into the
+// wave's [16][WS] LDS stripe and read back with lane = channel; the products
+// of that path's t run per edge as in the kernels above, with the
+// accumulators in registers.  The sender (or G) rows a path needs are
+// re-read per path: they stay in the caches, and holding sixteen edges of
+// them would take 64 to 256 registers.
+//
+// The B operand comes from global memory: a channel block's slice of Wr is
+// P x 16 KB, all of a CU's LDS at P = 10, while the whole matrix is 320 KB
+// and stays in L2.  The caller packs it once so every load is one coalesced
+// float4 per lane:
+//     Wa[p][cb][nt][g][q][j][i] = Wr[p C + 64 cb + 16 nt + j, 16 q + 4 g + i]
+//     Wb[p][cb][jt][g][q][n][i] = Wr[p C + 64 cb + 16 q + 4 g + i, 16 jt + n]
+// (Wa for w, Wb for dh).  MFMA step s = 4 g + i multiplies the k = 16 q + s
+// of the four lane quarters: the K order is permuted the same way on both
+// operands, which a dot product does not see.
+//
+// bwd_edge keeps G[n] in registers.  Per (edge, path) it overwrites the
+// lane's w in the stripe by its dw, takes the channel sums D[t] of the
+// path's t with the butterfly (lane j ends with value rev6(j)) and stores
+// them in the wave's D stripe.  After the dw of a path is complete the
+// stripe is the A operand of the dh tile, accumulated over the paths in 16
+// registers and written once per tile to this channel block's dhp slice.
+// After the last path lane (u, k2 quad) takes dY[e_u, k2] = sum_t K[t,k2]
+// D[u][t] from LDS.  A partial tile repeats its last edge in the unused
+// rows, which are computed and never stored.
+// ---------------------------------------------------------------------------
+
+constexpr int ETILE = 16;
+constexpr int RH = 64;                  // width of h
+constexpr int WS = 68;                  // stripe row: b128 reads of 16 rows spread over the banks
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// first t of path p
+template <int LS>
+constexpr int path_t0(int p) {
+    int t = 0;
+    while (TAB<LS>.tp[t] != p) ++t;
+    return t;
+}
+
+// number of t of path p
+template <int LS>
+constexpr int path_nt(int p) {
+    return (2 * TAB<LS>.l1[p] + 1) * (2 * TAB<LS>.l3[p] + 1);
+}
+
+// 16 consecutive floats of a row, as this lane's share of an A operand
+__device__ __forceinline__ void load16(float (&a)[16], const float* p) {
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 v = p4[g];
+        a[4 * g] = v.x; a[4 * g + 1] = v.y; a[4 * g + 2] = v.z;
+        a[4 * g + 3] = v.w;
+    }
+}
+
+// stripe[16][WS] = A[16 x 64] * the packed slice at wa (4 column tiles)
+__device__ __forceinline__ void w_tile(const float (&a)[16],
+                                       const float4* __restrict__ wa,
+                                       float* stripe, int lane) {
+    const int q = lane >> 4, j = lane & 15;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        float4 b[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) b[g] = wa[(nt * 4 + g) * 64 + lane];
+        f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * g], b[g].x, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * g + 1], b[g].y, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * g + 2], b[g].z, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * g + 3], b[g].w, d, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            stripe[(4 * q + r) * WS + nt * 16 + j] = d[r];
+    }
+}
+
+// forward (TR = false) and bwd_node (TR = true) of k_mace_conv, w from h
+template <int LS, bool TR>
+__global__ __launch_bounds__(BLOCK)
+void k_mace_conv_rad(
+        const float* __restrict__ A, const float* __restrict__ h,
+        const float4* __restrict__ Wa, const float* __restrict__ Y,
+        const float* __restrict__ K, const int32_t* __restrict__ idx,
+        const int32_t* __restrict__ perm, const int32_t* __restrict__ row_ptr,
+        float* __restrict__ out, int64_t N, int32_t C) {
+    constexpr int P = TAB<LS>.P, T = TAB<LS>.T, R = LS ? 4 : 1;
+    constexpr int RA = TR ? 16 : R, RO = TR ? R : 16;
+    __shared__ __attribute__((aligned(16))) float ws[WAVES][ETILE * WS];
+    __shared__ __attribute__((aligned(16))) float ycs[WAVES][ETILE * T];
+    __shared__ __attribute__((aligned(16))) float kl[KRows<LS>::FLOATS];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    KRows<LS> kr;
+    kr.init(kl, K, lane);
+    float* stripe = ws[wid];
+    float* ycw = ycs[wid];
+    const int32_t CB = C >> 6;
+    const int64_t work = N * CB;
+    const int64_t CA = RA * (int64_t)C;
+    for (int64_t wk = (int64_t)blockIdx.x * WAVES + wid; wk < work;
+         wk += (int64_t)gridDim.x * WAVES) {
+        const int64_t n = wk / CB;
+        const int32_t cb = (int32_t)(wk - n * CB);
+        const int32_t c = cb * 64 + lane;
+        const int32_t p0 = row_ptr[n], p1 = row_ptr[n + 1];
+        float acc[RO];
+#pragma unroll
+        for (int r = 0; r < RO; ++r) acc[r] = 0.0f;
+        for (int32_t pt = p0; pt < p1; pt += ETILE) {
+            const int nv = p1 - pt < ETILE ? p1 - pt : ETILE;
+            float ha[16];
+            {
+                const int32_t pp = pt + (lane & 15) < p1 ? pt + (lane & 15)
+                                                         : p1 - 1;
+                const int32_t e = TR ? perm[pp] : pp;
+                load16(ha, h + (int64_t)e * RH + (lane >> 4) * 16);
+            }
+            for (int u = 0; u < nv; ++u) {
+                const int32_t e = TR ? perm[pt + u] : pt + u;
+                kr.put_yc(ycw + u * T, Y + (int64_t)e * 16);
+            }
+            // a real loop over the paths: unrolled, the scheduler hoists
+            // every path's B loads to the top and spills
+#pragma unroll 1
+            for (int pr = 0; pr < P; ++pr) {
+              w_tile(ha, Wa + ((int64_t)pr * CB + cb) * 1024, stripe, lane);
+              wave_lds_sync();
+              static_for<0, P>([&](auto pc) {
+                constexpr int p = decltype(pc)::value;
+                if (pr != p) return;
+                constexpr int l1 = TAB<LS>.l1[p], l3 = TAB<LS>.l3[p];
+                constexpr int d1 = 2 * l1 + 1, d3 = 2 * l3 + 1;
+                constexpr int tb = path_t0<LS>(p);
+                constexpr int la = TR ? l3 : l1, da = TR ? d3 : d1;
+#pragma unroll 2
+                for (int u = 0; u < nv; ++u) {
+                    const int32_t e = TR ? perm[pt + u] : pt + u;
+                    const float* ap = A + (int64_t)idx[e] * CA
+                                      + (int64_t)(la * la) * C + c;
+                    float a[da];
+#pragma unroll
+                    for (int r = 0; r < da; ++r) a[r] = ap[(int64_t)r * C];
+                    const float w = stripe[u * WS + lane];
+                    const float* yc = ycw + u * T + tb;
+                    if constexpr (TR) {
+#pragma unroll
+                        for (int k3 = 0; k3 < d3; ++k3) {
+                            const float wg = w * a[k3];
+#pragma unroll
+                            for (int k1 = 0; k1 < d1; ++k1)
+                                acc[l1 * l1 + k1] = fmaf(
+                                    wg, yc[k1 * d3 + k3], acc[l1 * l1 + k1]);
+                        }
+                    } else {
+#pragma unroll
+                        for (int k1 = 0; k1 < d1; ++k1) {
+                            const float wx = w * a[k1];
+#pragma unroll
+                            for (int k3 = 0; k3 < d3; ++k3)
+                                acc[l3 * l3 + k3] = fmaf(
+                                    wx, yc[k1 * d3 + k3], acc[l3 * l3 + k3]);
+                        }
+                    }
+                }
+              });
+              wave_lds_sync();
+            }
+        }
+        float* op = out + n * (RO * (int64_t)C) + c;
+#pragma unroll
+        for (int r = 0; r < RO; ++r) op[(int64_t)r * C] = acc[r];
+    }
+}
+
+template <int LS>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+void k_mace_conv_rad_bwd_edge(
+        const float* __restrict__ G, const float* __restrict__ xs,
+        const float* __restrict__ h, const float4* __restrict__ Wa,
+        const float4* __restrict__ Wb, const float* __restrict__ Y,
+        const float* __restrict__ K, const int32_t* __restrict__ src,
+        const int32_t* __restrict__ row_ptr, float* __restrict__ dhp,
+        float* __restrict__ dYp, int64_t N, int64_t E, int32_t C) {
+    constexpr int P = TAB<LS>.P, T = TAB<LS>.T, R = LS ? 4 : 1;
+    constexpr int DS = T + 1;           // odd: 16 rows on 16 banks
+    __shared__ __attribute__((aligned(16))) float ws[WAVES][ETILE * WS];
+    __shared__ __attribute__((aligned(16))) float ycs[WAVES][ETILE * T];
+    __shared__ __attribute__((aligned(16))) float dss[WAVES][ETILE * DS];
+    __shared__ __attribute__((aligned(16))) float kl[KRows<LS>::FLOATS];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    KRows<LS> kr;
+    kr.init(kl, K, lane);
+    float* stripe = ws[wid];
+    float* ycw = ycs[wid];
+    float* dsw = dss[wid];
+    const int q = lane >> 4, j = lane & 15;
+    const int32_t CB = C >> 6;
+    const int64_t work = N * CB;
+    const int64_t C16 = 16 * (int64_t)C, CR = R * (int64_t)C;
+    for (int64_t wk = (int64_t)blockIdx.x * WAVES + wid; wk < work;
+         wk += (int64_t)gridDim.x * WAVES) {
+        const int64_t n = wk / CB;
+        const int32_t cb = (int32_t)(wk - n * CB);
+        const int32_t c = cb * 64 + lane;
+        const int32_t p0 = row_ptr[n], p1 = row_ptr[n + 1];
+        if (p0 == p1) continue;
+        float g[16];
+        const float* gp = G + n * C16 + c;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g[r] = gp[(int64_t)r * C];
+        for (int32_t pt = p0; pt < p1; pt += ETILE) {
+            const int nv = p1 - pt < ETILE ? p1 - pt : ETILE;
+            float ha[16];
+            {
+                const int32_t e = pt + j < p1 ? pt + j : p1 - 1;
+                load16(ha, h + (int64_t)e * RH + q * 16);
+            }
+            for (int u = 0; u < nv; ++u)
+                kr.put_yc(ycw + u * T, Y + (int64_t)(pt + u) * 16);
+            f32x4 dh[4];
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt)
+                dh[jt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+            for (int pr = 0; pr < P; ++pr) {
+              w_tile(ha, Wa + ((int64_t)pr * CB + cb) * 1024, stripe, lane);
+              wave_lds_sync();
+              static_for<0, P>([&](auto pc) {
+                constexpr int p = decltype(pc)::value;
+                if (pr != p) return;
+                constexpr int l1 = TAB<LS>.l1[p], l3 = TAB<LS>.l3[p];
+                constexpr int d1 = 2 * l1 + 1, d3 = 2 * l3 + 1;
+                constexpr int tb = path_t0<LS>(p), NV = d1 * d3;
+                for (int u = 0; u < nv; ++u) {
+                    const float* xp = xs + (int64_t)src[pt + u] * CR
+                                      + (int64_t)(l1 * l1) * C + c;
+                    float x[d1], v[NV];
+#pragma unroll
+                    for (int k1 = 0; k1 < d1; ++k1) x[k1] = xp[(int64_t)k1 * C];
+                    const float w = stripe[u * WS + lane];
+                    const float* yc = ycw + u * T + tb;
+                    float dwv = 0.0f;
+#pragma unroll
+                    for (int k1 = 0; k1 < d1; ++k1)
+#pragma unroll
+                        for (int k3 = 0; k3 < d3; ++k3) {
+                            const float xg = x[k1] * g[l3 * l3 + k3];
+                            dwv = fmaf(yc[k1 * d3 + k3], xg, dwv);
+                            v[k1 * d3 + k3] = w * xg;
+                        }
+                    stripe[u * WS + lane] = dwv;
+                    bfly_rest<NV, 32>(v, lane);
+                    if (kr.t0 < NV) dsw[u * DS + tb + kr.t0] = v[0];
+                }
+              });
+              wave_lds_sync();
+              {
+                // dh += dw[16 edges x 64 channels] * Wr slice
+                float da[16];
+                load16(da, stripe + j * WS + q * 16);
+                const float4* wb = Wb + ((int64_t)pr * CB + cb) * 1024;
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt) {
+                    float4 b[4];
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq)
+                        b[gq] = wb[(jt * 4 + gq) * 64 + lane];
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        dh[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            da[4 * gq], b[gq].x, dh[jt], 0, 0, 0);
+                        dh[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            da[4 * gq + 1], b[gq].y, dh[jt], 0, 0, 0);
+                        dh[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            da[4 * gq + 2], b[gq].z, dh[jt], 0, 0, 0);
+                        dh[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            da[4 * gq + 3], b[gq].w, dh[jt], 0, 0, 0);
+                    }
+                }
+              }
+              wave_lds_sync();
+            }
+            // dh rows 4 q + r, columns 16 jt + j
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (4 * q + r < nv) {
+                    float* dp = dhp + ((int64_t)cb * E + pt + 4 * q + r) * RH + j;
+#pragma unroll
+                    for (int jt = 0; jt < 4; ++jt) dp[jt * 16] = dh[jt][r];
+                }
+            // dY[e_u, 4 kq ..] = sum_t K[t, 4 kq ..] D[u][t]
+            {
+                const int u = lane >> 2, kq = lane & 3;
+                float4 dy = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 4
+                for (int t = 0; t < T; ++t) {
+                    const int row = (t & 64)      // as KRows::init places it
+                        + (int)(__brev((unsigned)(t & 63)) >> 26);
+                    const float4 k4 = reinterpret_cast<const float4*>(
+                        kl + row * KRows<LS>::KS)[kq];
+                    const float d = dsw[u * DS + t];
+                    dy.x = fmaf(k4.x, d, dy.x); dy.y = fmaf(k4.y, d, dy.y);
+                    dy.z = fmaf(k4.z, d, dy.z); dy.w = fmaf(k4.w, d, dy.w);
+                }
+                if (u < nv)
+                    reinterpret_cast<float4*>(
+                        dYp + ((int64_t)cb * E + pt + u) * 16)[kq] = dy;
+            }
+            wave_lds_sync();
+        }
+    }
+}
+
 int conv_check(int64_t N, int32_t C, int32_t ls, const char* name) {
     if (N < 0 || C <= 0 || C % 64 != 0 || (ls != 0 && ls != 1)) {
         char buf[128];
@@ -438,6 +771,16 @@ int conv_check(int64_t N, int32_t C, int32_t ls, const char* name) {
         return -1;
     }
     return 0;
+}
+
+int rad_check(int64_t N, int32_t C, int32_t H, int32_t ls, const char* name) {
+    if (H != RH) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "%s: H must be %d", name, RH);
+        dm_set_last_error(buf);
+        return -1;
+    }
+    return conv_check(N, C, ls, name);
 }
 
 int conv_launched() {
@@ -505,6 +848,70 @@ int dm_mace_conv_bwd_node_f32(const float* G, const float* tp_w,
     else
         k_mace_conv<1, true, 1><<<nb, BLOCK, 0, s>>>(
             G, tp_w, Y, K, dst, src_perm, src_row_ptr, dxs, N, C);
+    return conv_launched();
+}
+
+int dm_mace_conv_rad_fwd_f32(const float* xs, const float* h, const float* Wa,
+                             const float* Y, const float* K,
+                             const int32_t* src, const int32_t* row_ptr,
+                             float* M, int64_t N, int32_t C, int32_t H,
+                             int32_t ls, uint64_t stream) {
+    if (int rc = rad_check(N, C, H, ls, "dm_mace_conv_rad_fwd_f32")) return rc;
+    if (N == 0) return 0;
+    const int nb = nblocks(N * (C / 64), WAVES);
+    hipStream_t s = (hipStream_t)stream;
+    const float4* wa = reinterpret_cast<const float4*>(Wa);
+    if (ls == 0)
+        k_mace_conv_rad<0, false><<<nb, BLOCK, 0, s>>>(
+            xs, h, wa, Y, K, src, nullptr, row_ptr, M, N, C);
+    else
+        k_mace_conv_rad<1, false><<<nb, BLOCK, 0, s>>>(
+            xs, h, wa, Y, K, src, nullptr, row_ptr, M, N, C);
+    return conv_launched();
+}
+
+int dm_mace_conv_rad_bwd_edge_f32(const float* G, const float* xs,
+                                  const float* h, const float* Wa,
+                                  const float* Wb, const float* Y,
+                                  const float* K, const int32_t* src,
+                                  const int32_t* row_ptr, float* dhp,
+                                  float* dYp, int64_t N, int64_t E, int32_t C,
+                                  int32_t H, int32_t ls, uint64_t stream) {
+    if (int rc = rad_check(N, C, H, ls, "dm_mace_conv_rad_bwd_edge_f32"))
+        return rc;
+    if (N == 0 || E == 0) return 0;
+    const int nb = nblocks(N * (C / 64), WAVES);
+    hipStream_t s = (hipStream_t)stream;
+    const float4* wa = reinterpret_cast<const float4*>(Wa);
+    const float4* wb = reinterpret_cast<const float4*>(Wb);
+    if (ls == 0)
+        k_mace_conv_rad_bwd_edge<0><<<nb, BLOCK, 0, s>>>(
+            G, xs, h, wa, wb, Y, K, src, row_ptr, dhp, dYp, N, E, C);
+    else
+        k_mace_conv_rad_bwd_edge<1><<<nb, BLOCK, 0, s>>>(
+            G, xs, h, wa, wb, Y, K, src, row_ptr, dhp, dYp, N, E, C);
+    return conv_launched();
+}
+
+int dm_mace_conv_rad_bwd_node_f32(const float* G, const float* h,
+                                  const float* Wa, const float* Y,
+                                  const float* K, const int32_t* dst,
+                                  const int32_t* src_perm,
+                                  const int32_t* src_row_ptr, float* dxs,
+                                  int64_t N, int32_t C, int32_t H, int32_t ls,
+                                  uint64_t stream) {
+    if (int rc = rad_check(N, C, H, ls, "dm_mace_conv_rad_bwd_node_f32"))
+        return rc;
+    if (N == 0) return 0;
+    const int nb = nblocks(N * (C / 64), WAVES);
+    hipStream_t s = (hipStream_t)stream;
+    const float4* wa = reinterpret_cast<const float4*>(Wa);
+    if (ls == 0)
+        k_mace_conv_rad<0, true><<<nb, BLOCK, 0, s>>>(
+            G, h, wa, Y, K, dst, src_perm, src_row_ptr, dxs, N, C);
+    else
+        k_mace_conv_rad<1, true><<<nb, BLOCK, 0, s>>>(
+            G, h, wa, Y, K, dst, src_perm, src_row_ptr, dxs, N, C);
     return conv_launched();
 }
 

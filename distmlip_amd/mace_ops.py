@@ -486,9 +486,10 @@ class _MaceConvFn(torch.autograd.Function):
 
 def conv_fused_available(inter: Interaction, Y: torch.Tensor, C: int, pd,
                          ops) -> bool:
-    """DM_MACE_CONV=split pins the gather + conv_tp_hip + scatter path."""
+    """DM_MACE_CONV=split pins the gather + conv_tp_hip + scatter path;
+    =radial asks for conv_radial_hip and falls back to this one."""
     import os
-    return (os.environ.get("DM_MACE_CONV", "fused") == "fused"
+    return (os.environ.get("DM_MACE_CONV", "fused") in ("fused", "radial")
             and os.environ.get("DM_MACE_TP", "hip") == "hip"
             and Y.is_cuda and Y.dtype == torch.float32
             and C % 64 == 0
@@ -514,6 +515,126 @@ def conv_fused_hip(inter: Interaction, x_up: Dict[int, torch.Tensor],
                           pd.src_row_ptr)
     return {l3: M[:, so3.L_OFF[l3]:so3.L_OFF[l3] + so3.L_DIMS[l3], :]
             .permute(0, 2, 1).contiguous() for l3 in range(4)}
+
+
+# ---------------------------------------------------------------------------
+# the fused convolution with the radial MLP's last layer inside: tp_w =
+# h @ Wr.T is formed per 16-edge tile on fp32 MFMA and never stored, and dw
+# goes straight into dh.  Per-edge state: h [E,64], Y [E,16], their gradients.
+# ---------------------------------------------------------------------------
+
+RADIAL_H = 64
+
+
+def _conv_wr_packed(inter: Interaction, C: int):
+    """The last radial weight Wr [P*C, 64] in the MFMA operand orders of
+    csrc/mace_conv.hip (Wa for w, Wb for dh; include/distmlip_hip.h);
+    cached on the module while frozen."""
+    Wr = inter.radial.layers[-1].weight
+    key = (Wr.device, Wr._version)
+    cached = getattr(inter, "_dm_wr_packed", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    P, CB = Wr.shape[0] // C, C // 64
+    W = Wr.detach()
+    Wa = W.view(P, CB, 4, 16, 4, 4, 4).permute(0, 1, 2, 5, 4, 3, 6)
+    Wb = W.view(P, CB, 4, 4, 4, 4, 16).permute(0, 1, 5, 3, 2, 6, 4)
+    packed = (Wa.contiguous(), Wb.contiguous())
+    if not Wr.requires_grad:
+        inter._dm_wr_packed = (key, packed)
+    return packed
+
+
+class _MaceConvRadialFn(torch.autograd.Function):
+    """_MaceConvFn with tp_w = h @ Wr.T computed inside the kernels: M from
+    xs [N,R,C], Y [E,16], h [E,64] and the packed Wr.  The backward gives
+    dxs, dY and dh; Wr is frozen.  Deterministic: no atomics."""
+
+    @staticmethod
+    def forward(ctx, xs, Y, h, Wa, Wb, K, ls, src, dst, row_ptr, src_perm,
+                src_row_ptr):
+        from distmlip_amd.ops import _check, _chk_f32, _fp, _ip, _stream, \
+            hip_lib
+        _chk_f32(xs, Y, h, Wa, Wb, K)
+        N, _, C = xs.shape
+        ctx.save_for_backward(xs, Y, h)
+        ctx.idx = (Wa, Wb, K, ls, src, dst, row_ptr, src_perm, src_row_ptr)
+        if Y.shape[0] == 0:
+            return xs.new_zeros(N, 16, C)
+        M = torch.empty(N, 16, C, dtype=xs.dtype, device=xs.device)
+        _check(hip_lib().dm_mace_conv_rad_fwd_f32(
+            _fp(xs), _fp(h), _fp(Wa), _fp(Y), _fp(K), _ip(src), _ip(row_ptr),
+            _fp(M), N, C, h.shape[1], ls, _stream()),
+            "dm_mace_conv_rad_fwd_f32")
+        return M
+
+    @staticmethod
+    def backward(ctx, G):
+        from distmlip_amd.ops import _check, _fp, _ip, _stream, hip_lib
+        xs, Y, h = ctx.saved_tensors
+        Wa, Wb, K, ls, src, dst, row_ptr, src_perm, src_row_ptr = ctx.idx
+        N, _, C = xs.shape
+        E, H = h.shape
+        dxs = dY = dh = None
+        if E == 0:
+            return (torch.zeros_like(xs), torch.zeros_like(Y),
+                    torch.zeros_like(h)) + (None,) * 9
+        G = G.contiguous()
+        if ctx.needs_input_grad[0]:
+            dxs = torch.empty_like(xs)
+            _check(hip_lib().dm_mace_conv_rad_bwd_node_f32(
+                _fp(G), _fp(h), _fp(Wa), _fp(Y), _fp(K), _ip(dst),
+                _ip(src_perm), _ip(src_row_ptr), _fp(dxs), N, C, H, ls,
+                _stream()), "dm_mace_conv_rad_bwd_node_f32")
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dhp = torch.empty(C // 64, E, H, dtype=h.dtype, device=h.device)
+            dYp = torch.empty(C // 64, E, 16, dtype=Y.dtype, device=Y.device)
+            _check(hip_lib().dm_mace_conv_rad_bwd_edge_f32(
+                _fp(G), _fp(xs), _fp(h), _fp(Wa), _fp(Wb), _fp(Y), _fp(K),
+                _ip(src), _ip(row_ptr), _fp(dhp), _fp(dYp), N, E, C, H, ls,
+                _stream()), "dm_mace_conv_rad_bwd_edge_f32")
+            dh = dhp[0] if C == 64 else dhp.sum(0)
+            dY = dYp[0] if C == 64 else dYp.sum(0)
+        return (dxs, dY, dh) + (None,) * 9
+
+
+def conv_radial_available(inter: Interaction, Y: torch.Tensor, C: int, pd,
+                          ops) -> bool:
+    """DM_MACE_CONV=radial, where the fused convolution can run, the radial
+    MLP's last layer is 64 wide and its weight frozen."""
+    import os
+    Wr = inter.radial.layers[-1].weight
+    return (os.environ.get("DM_MACE_CONV", "fused") == "radial"
+            and conv_fused_available(inter, Y, C, pd, ops)
+            and Wr.shape[1] == RADIAL_H and not Wr.requires_grad)
+
+
+def conv_radial_hip(inter: Interaction, x_up: Dict[int, torch.Tensor],
+                    Y: torch.Tensor, h: torch.Tensor, pd
+                    ) -> Dict[int, torch.Tensor]:
+    """conv_fused_hip from h [E,64], the output of inter.radial.layers[:-1]
+    with their SiLUs, in place of tp_w = h @ Wr.T (see _MaceConvRadialFn)."""
+    paths_key = tuple(inter.paths)
+    ls = _conv_path_lists().index(paths_key)
+    K = _conv_K(paths_key, str(Y.device))
+    xs = torch.cat([x_up[l].permute(0, 2, 1) for l in sorted(x_up)],
+                   dim=1).contiguous()              # [N, R, C]
+    assert xs.shape[1] == (1, 4)[ls], xs.shape
+    Wa, Wb = _conv_wr_packed(inter, xs.shape[2])
+    M = _MaceConvRadialFn.apply(xs, Y.contiguous(), h.contiguous(), Wa, Wb,
+                                K, ls, pd.src, pd.dst, pd.row_ptr,
+                                pd.src_perm, pd.src_row_ptr)
+    return {l3: M[:, so3.L_OFF[l3]:so3.L_OFF[l3] + so3.L_DIMS[l3], :]
+            .permute(0, 2, 1).contiguous() for l3 in range(4)}
+
+
+def radial_hidden(inter: Interaction, edge_feats: torch.Tensor
+                  ) -> torch.Tensor:
+    """h [E,64]: the radial MLP up to its last layer, SiLUs included."""
+    x = edge_feats
+    for lin in inter.radial.layers[:-1]:
+        x = torch.nn.functional.silu(lin(x))
+    return x
 
 
 # ---------------------------------------------------------------------------

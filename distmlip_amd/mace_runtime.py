@@ -192,7 +192,13 @@ class MaceSpmdEngine:
                 x_up = mace_ops.irreps_linear(_inter.linear_up, xd)
                 use_hip = mace_ops.conv_tp_hip_available(_inter, Y, C)
                 E_tot = len(pd.src)
-                if E_tot > chunk_e:
+                if mace_ops.conv_radial_available(_inter, Y, C, pd, ops):
+                    # the fused convolution with the last radial layer
+                    # inside: no [E, P, C] array at all, so no chunking
+                    # at any E
+                    h = mace_ops.radial_hidden(_inter, edge_feats)
+                    m = mace_ops.conv_radial_hip(_inter, x_up, Y, h, pd)
+                elif E_tot > chunk_e:
                     # this branch stays on the per-edge kernels: the fused
                     # convolution walks the src CSR in its reverse pass, and
                     # a node-range chunk has no src CSR of its own

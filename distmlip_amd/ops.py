@@ -186,6 +186,19 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_mace_conv_bwd_node_f32.argtypes = [fp, fp, fp, fp, ip, ip, ip,
                                                   fp, c_int64, c_int32,
                                                   c_int32, c_uint64]
+        # the same with the last radial layer inside (h, packed Wr, H)
+        lib.dm_mace_conv_rad_fwd_f32.restype = c_int32
+        lib.dm_mace_conv_rad_fwd_f32.argtypes = [
+            fp, fp, fp, fp, fp, ip, ip, fp, c_int64, c_int32, c_int32,
+            c_int32, c_uint64]
+        lib.dm_mace_conv_rad_bwd_edge_f32.restype = c_int32
+        lib.dm_mace_conv_rad_bwd_edge_f32.argtypes = [
+            fp, fp, fp, fp, fp, fp, fp, ip, ip, fp, fp, c_int64, c_int64,
+            c_int32, c_int32, c_int32, c_uint64]
+        lib.dm_mace_conv_rad_bwd_node_f32.restype = c_int32
+        lib.dm_mace_conv_rad_bwd_node_f32.argtypes = [
+            fp, fp, fp, fp, fp, ip, ip, ip, fp, c_int64, c_int32, c_int32,
+            c_int32, c_uint64]
         cf = ctypes.c_float
         lib.dm_edge_geom_rbf_fwd_f32.restype = c_int32
         lib.dm_edge_geom_rbf_fwd_f32.argtypes = [fp, ip, ip, fp, fp, cf,

@@ -621,6 +621,39 @@ int dm_mace_conv_bwd_node_f32(const float* G, const float* tp_w,
                               int64_t N, int32_t C, int32_t ls,
                               uint64_t stream);
 
+/* The same three passes with the radial MLP's last layer computed inside on
+ * fp32 MFMA: w[e,p,c] = sum_j h[e,j] Wr[p C + c, j] takes the place of tp_w
+ * and is never stored, nor is dw; bwd_edge returns
+ *   dhp[b,e,j] = sum_p sum_{c in block b} dw[e,p,c] Wr[p C + c, j]
+ * one [E,H] slice per 64-channel block b (dh is their sum) beside dYp.
+ * h [E,H] with H == 64.  Wr [P C, H] is passed packed in the operand order of
+ * v_mfma_f32_16x16x4_f32, both [P, C/64, 4, 4, 4, 16, 4] (P C H floats):
+ *   Wa[p][b][nt][g][q][j][i] = Wr[p C + 64 b + 16 nt + j, 16 q + 4 g + i]
+ *   Wb[p][b][jt][g][q][n][i] = Wr[p C + 64 b + 16 q + 4 g + i, 16 jt + n]
+ * Everything else as in dm_mace_conv_*: same mapping (rows walked in tiles
+ * of 16 edges), no atomics, bit-identical from run to run, zeros for rows
+ * without edges.  H != 64, C not a positive multiple of 64 or ls not 0 or 1
+ * return -1 and launch nothing. */
+int dm_mace_conv_rad_fwd_f32(const float* xs, const float* h, const float* Wa,
+                             const float* Y, const float* K,
+                             const int32_t* src, const int32_t* row_ptr,
+                             float* M, int64_t N, int32_t C, int32_t H,
+                             int32_t ls, uint64_t stream);
+int dm_mace_conv_rad_bwd_edge_f32(const float* G, const float* xs,
+                                  const float* h, const float* Wa,
+                                  const float* Wb, const float* Y,
+                                  const float* K, const int32_t* src,
+                                  const int32_t* row_ptr, float* dhp,
+                                  float* dYp, int64_t N, int64_t E, int32_t C,
+                                  int32_t H, int32_t ls, uint64_t stream);
+int dm_mace_conv_rad_bwd_node_f32(const float* G, const float* h,
+                                  const float* Wa, const float* Y,
+                                  const float* K, const int32_t* dst,
+                                  const int32_t* src_perm,
+                                  const int32_t* src_row_ptr, float* dxs,
+                                  int64_t N, int32_t C, int32_t H, int32_t ls,
+                                  uint64_t stream);
+
 /* Integrator kernels of the native MD / relaxation driver
  * (distmlip_amd/md.py; the reference drives ASE's integrators instead,
  * implementations/matgl/ase.py:130-490).  State is fp64: wrapped fractional
