@@ -264,6 +264,8 @@ def symmetric_contract(prod: ProductBasis, x: Dict[int, torch.Tensor],
     like = next(iter(x.values()))
     if symc_hip_available(x, prod):
         return symmetric_contract_hip(prod, x, species, correlation)
+    if symc_tree_available(x, prod):
+        return symmetric_contract_tree(prod, x, species, correlation)
     N, C = like.shape[0], like.shape[1]
     dts, devs = str(like.dtype).split(".")[-1], str(like.device)
     out = {}
@@ -781,4 +783,174 @@ def symc_hip_available(x: Dict[int, torch.Tensor],
     return (os.environ.get("DM_MACE_SYMC", "hip") == "hip"
             and like.is_cuda and like.shape[1] in (64, 128)
             and sorted(x) == [0, 1, 2, 3]
+            and not any(p.requires_grad for p in prod.weights.values()))
+
+
+# ---------------------------------------------------------------------------
+# tree-factored HIP symmetric contraction (csrc/mace_symc.hip): one wave per
+# (node, 64-channel block), the polynomial evaluated through its coupling
+# trees as two-factor products, any C % 64 == 0.  Same W table, layouts and
+# frozen-weight convention as the flat kernel above.
+# ---------------------------------------------------------------------------
+
+@lru_cache(maxsize=None)
+def _symc_tree_tables(out_ls, correlation: int, device_str: str):
+    """The int32 table of dm_mace_symc_tree_* (layout: csrc/mace_symc.hip)
+    for the trees of _symc_nz, in its wrow order.  Returns
+    (tab, T, S_out, sizes); sizes counts groups, trees, pairs, segs and
+    stage-1 / stage-2 / transposed entries."""
+    import numpy as np
+    assert correlation <= 3, correlation
+    ONE = 16                        # the x row that holds 1
+    nz, segs, pairs, pair_id = [], [], [], {}
+
+    def add_segs(ents, dsts):
+        """ents (dst, p, q, coef) as one seg per dst; -> [beg, end)"""
+        beg = len(segs)
+        for d in dsts:
+            b = len(nz)
+            nz.extend(e[1:] for e in ents if e[0] == d)
+            segs.append((d, b, len(nz), 0))
+        return beg, len(segs)
+
+    def cg_ents(o1, o2, CG):
+        return [(o1 + a, o2 + b, m, CG[a, b, m])
+                for a, b, m in np.argwhere(np.abs(CG) > 1e-12)]
+
+    def pair(key, ents):
+        """stage-1 entries (a, b, mL, coef) of one pair, stored once"""
+        if key not in pair_id:
+            rp = []
+            for m in range(9):
+                rp.append(len(nz))
+                nz.extend((a, b, c) for a, b, mm, c in ents if mm == m)
+            rp.append(len(nz))
+            tr = ([(a, m, b, c) for a, b, m, c in ents if a != ONE]
+                  + [(b, m, a, c) for a, b, m, c in ents if b != ONE])
+            rp.extend(add_segs(tr, sorted({e[0] for e in tr})))
+            pair_id[key] = len(pairs)
+            pairs.append(rp)
+        return pair_id[key]
+
+    groups = {}                     # (lo, L, l3) -> [(wrow, pair)]
+    o_offs, wrow, o_off, n_s1 = {}, 0, 0, 0
+    for lo in out_ls:
+        o_offs[lo] = o_off
+        for nu in range(1, correlation + 1):
+            for tr in so3.symmetric_basis_trees(nu, lo)[0]:
+                if nu == 1:
+                    pid = pair((lo,), [(so3.L_OFF[lo] + m, ONE, m, 1.0)
+                                       for m in range(2 * lo + 1)])
+                    gkey = (lo, lo, None)
+                else:
+                    l1, l2, L = tr[0], tr[1], (lo if nu == 2 else tr[2])
+                    pid = pair((l1, l2, L),
+                               cg_ents(so3.L_OFF[l1], so3.L_OFF[l2],
+                                       so3.real_cg(l1, l2, L)))
+                    gkey = (lo, L, None if nu == 2 else tr[3])
+                assert 2 * gkey[1] + 1 <= 9, gkey
+                groups.setdefault(gkey, []).append((wrow, pid))
+                n_s1 += pairs[pid][9] - pairs[pid][0]
+                wrow += 1
+        o_off += 2 * lo + 1
+    assert o_off <= 4, out_ls
+    trees, grows, n_s2 = [], [], 0
+    for (lo, L, l3), tl in groups.items():
+        if l3 is None:              # identity against the row of ones
+            s2 = [(o_offs[lo] + m, m, ONE, 1.0) for m in range(2 * lo + 1)]
+        else:
+            s2 = [(o_offs[lo] + o, m, so3.L_OFF[l3] + k, c)
+                  for m, k, o, c in cg_ents(0, 0, so3.real_cg(L, l3, lo))]
+        n_s2 += len(s2)
+        row = [len(trees), len(trees) + len(tl)]
+        trees.extend(tl)
+        row.extend(add_segs([(o, m, k, c) for o, m, k, c in s2],
+                            sorted({e[0] for e in s2})))
+        row.extend(add_segs([(m, o, k, c) for o, m, k, c in s2],
+                            range(2 * L + 1)))
+        bk = [(k, o, m, c) for o, m, k, c in s2 if k != ONE]
+        row.extend(add_segs(bk, sorted({e[0] for e in bk})))
+        grows.append(row)
+    ent = np.asarray([(p, q) for p, q, _ in nz], dtype=np.int64)
+    assert ent.min() >= 0 and ent.max() <= ONE and len(nz) < 2 ** 31
+    assert all(0 <= s[0] < 16 and 0 <= s[1] <= s[2] <= len(nz) for s in segs)
+    nzw = np.empty((len(nz), 2), dtype=np.int32)
+    nzw[:, 0] = ent[:, 0] | (ent[:, 1] << 8)
+    nzw[:, 1] = np.asarray([c for _, _, c in nz], dtype=np.float32) \
+        .view(np.int32)
+    parts = [np.asarray(a, dtype=np.int32).reshape(-1)
+             for a in (grows, trees, pairs, segs)]
+    offs = [16]
+    for a in parts:
+        offs.append(offs[-1] + a.size)
+    pad = offs[-1] % 2              # nz is read as int2: 8-byte aligned
+    offs[-1] += pad
+    head = np.zeros(16, dtype=np.int32)
+    head[0], head[1:6] = len(grows), offs
+    tab = np.concatenate([head] + parts + [np.zeros(pad, np.int32),
+                                           nzw.reshape(-1)])
+    sizes = {"groups": len(grows), "trees": len(trees), "pairs": len(pairs),
+             "segs": len(segs), "stage1_per_tree": int(n_s1),
+             "stage2": n_s2, "nz": len(nz), "int32": int(tab.size)}
+    return (torch.tensor(tab, device=torch.device(device_str)), wrow, o_off,
+            sizes)
+
+
+class _MaceSymcTreeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xs, elem, W, tab, S_out):
+        from distmlip_amd.ops import _check, _fp, _ip, _stream, hip_lib
+        N, _, C = xs.shape
+        out = torch.empty(N, S_out, C, dtype=xs.dtype, device=xs.device)
+        _check(hip_lib().dm_mace_symc_tree_fwd_f32(
+            _fp(xs), _ip(elem), _fp(W), _ip(tab), _fp(out), N, C,
+            W.shape[1], S_out, _stream()), "dm_mace_symc_tree_fwd_f32")
+        ctx.save_for_backward(xs, elem, W, tab)
+        ctx.S_out = S_out
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        from distmlip_amd.ops import _check, _fp, _ip, _stream, hip_lib
+        xs, elem, W, tab = ctx.saved_tensors
+        N, _, C = xs.shape
+        dx = torch.empty_like(xs)
+        _check(hip_lib().dm_mace_symc_tree_bwd_f32(
+            _fp(go.contiguous()), _fp(xs), _ip(elem), _fp(W), _ip(tab),
+            _fp(dx), N, C, W.shape[1], ctx.S_out, _stream()),
+            "dm_mace_symc_tree_bwd_f32")
+        return dx, None, None, None, None
+
+
+def symmetric_contract_tree(prod: ProductBasis, x: Dict[int, torch.Tensor],
+                            species: torch.Tensor, correlation: int
+                            ) -> Dict[int, torch.Tensor]:
+    like = next(iter(x.values()))
+    xs = torch.cat([x[l].permute(0, 2, 1) for l in sorted(x)],
+                   dim=1).contiguous()            # [N, 16, C]
+    tab, T, S_out, _ = _symc_tree_tables(tuple(prod.out_ls), correlation,
+                                         str(like.device))
+    W = _symc_wcat(prod, correlation)
+    assert W.shape[1] == T and xs.shape[1] == 16, (W.shape, xs.shape)
+    elem = species.to(torch.int32).contiguous()
+    out = _MaceSymcTreeFn.apply(xs, elem, W, tab, S_out)
+    res, off = {}, 0
+    for lo in prod.out_ls:
+        do = 2 * lo + 1
+        res[lo] = out[:, off:off + do, :].permute(0, 2, 1).contiguous()
+        off += do
+    return res
+
+
+def symc_tree_available(x: Dict[int, torch.Tensor],
+                        prod: ProductBasis) -> bool:
+    """DM_MACE_SYMC=tree, or unset / hip at a width the flat kernel does
+    not serve; torch pins the composition."""
+    import os
+    like = next(iter(x.values()))
+    return (os.environ.get("DM_MACE_SYMC", "hip") in ("hip", "tree")
+            and like.is_cuda and like.dtype == torch.float32
+            and like.shape[1] > 0 and like.shape[1] % 64 == 0
+            and sorted(x) == [0, 1, 2, 3]
+            and sum(2 * lo + 1 for lo in prod.out_ls) <= 4
             and not any(p.requires_grad for p in prod.weights.values()))

@@ -158,6 +158,15 @@ def hip_lib() -> ctypes.CDLL:
         lib.dm_mace_symc_bwd_f32.argtypes = [fp, fp, ip, fp, ip, fp,
                                              c_int32, fp, c_int64, c_int32,
                                              c_int32, c_int32, c_uint64]
+        # tree-factored symmetric contraction (csrc/mace_symc.hip)
+        lib.dm_mace_symc_tree_fwd_f32.restype = c_int32
+        lib.dm_mace_symc_tree_fwd_f32.argtypes = [fp, ip, fp, ip, fp, c_int64,
+                                                  c_int32, c_int32, c_int32,
+                                                  c_uint64]
+        lib.dm_mace_symc_tree_bwd_f32.restype = c_int32
+        lib.dm_mace_symc_tree_bwd_f32.argtypes = [fp, fp, ip, fp, ip, fp,
+                                                  c_int64, c_int32, c_int32,
+                                                  c_int32, c_uint64]
         lib.dm_mace_tp_bwd_f32.restype = c_int32
         lib.dm_mace_tp_bwd_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp,
                                            ip, fp, c_int32, fp, fp, fp, fp,

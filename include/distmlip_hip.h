@@ -480,6 +480,32 @@ int dm_mace_symc_bwd_f32(const float* go, const float* x,
                          float* dx, int64_t N, int32_t C, int32_t T,
                          int32_t S_out, uint64_t stream);
 
+/* MACE symmetric contraction through its coupling trees
+ * (csrc/mace_symc.hip): the polynomial of dm_mace_symc_*, evaluated as pair
+ * products q = CG(l1,l2,L) x x, v = sum over the trees of a group (L,l3,lo) of
+ * W[elem,wrow,:] q, and out += CG(L,l3,lo) v x; nu <= 2 trees couple against
+ * a constant row of ones.  Results differ from dm_mace_symc_* in rounding only.
+ * x [N,16,C] l-major rows, W [n_elem,T,C] in the same wrow order, out and
+ * go = dL/dout [N,S_out,C], dx [N,16,C].  tab is the int32 table that
+ * mace_ops._symc_tree_tables builds (header, groups, trees, pairs, segs,
+ * entries: layout in the file header); the kernels trust its indices and
+ * elem[n] < n_elem.  Weights are frozen, so bwd produces dx only.
+ *
+ * One wave per (node, 64-channel block), lane = channel, all state in
+ * registers and the wave's own LDS rows: no atomics, every row written once,
+ * results bit-identical from run to run.  N == 0 returns 0 with no launch.
+ * C not a positive multiple of 64, or S_out outside 1..4, returns -1 and
+ * launches nothing. */
+int dm_mace_symc_tree_fwd_f32(const float* x, const int32_t* elem,
+                              const float* W, const int32_t* tab, float* out,
+                              int64_t N, int32_t C, int32_t T, int32_t S_out,
+                              uint64_t stream);
+int dm_mace_symc_tree_bwd_f32(const float* go, const float* x,
+                              const int32_t* elem, const float* W,
+                              const int32_t* tab, float* dx, int64_t N,
+                              int32_t C, int32_t T, int32_t S_out,
+                              uint64_t stream);
+
 /* eSCN/UMA per-edge Wigner rotation family (round 2): replaces the
  * per-edge D-matrix bmms of the reference's UMA path
  * (escn_md.py:283-291 rotation setup; applications around every SO(2)
